@@ -2,7 +2,7 @@
 """Stage-0 training throughput of the nerf2mesh hot path on MI355X (BASELINE.json: "train rays/sec & samples/sec,
 Lego 800x800 stage-0").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one full stage-0 iteration of the reference's loop (nerf/utils.py:1152-1180) on the lego recipe
@@ -18,13 +18,18 @@ lambda_specular * mean(sum(specular^2)), nerf/utils.py:733-737).  The default `-
 switch: the line reports the steady-state step (`config.shading` = "full").  `--diffuse` times the warm-up phase instead (pretrain 300,
 steps 306.. as rounds 1-2 reported) and says so in `config.shading`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-  roofline     -- the dominant HIP kernel of the step: algorithmic bytes per launch / mean launch duration, measured with
-                  hipEvents attached to the kernel dispatches on the launch stream inside the timed region (n2m_prof_*), against the
-                  8 TB/s HBM peak and against a stream copy timed in the same process (peak_measured)
+Prints ONE JSON line on rank 0.  A plain run sets up, pre-trains and warms up, times the `--steps` steps and prints the headline
+(`value` samples/s, `ms_per_step`); nothing else is measured.  `--full` adds what the headline does not need, each a reported extra:
+  kernels /    -- per-kernel hipEvents attached to the kernel dispatches inside the timed region (n2m_prof_*); roofline = the dominant
+  roofline        HIP kernel of the step: algorithmic bytes per launch / mean launch duration against the 8 TB/s HBM peak and against a
+                  stream copy timed in the same process (peak_measured)
+  long_run     -- 192 more steps behind the timed window (the occupancy refresh at its long-run share)
   cpu_baseline -- the CPU oracle (oracle/n2m_oracle.c, OpenMP, 32 threads) + PyTorch-CPU MLPs timed on a bounded sample of the same
                   workload (rank 0, N=1 only); cpu_baseline_reference -- the same iteration on the reference's own kernels compiled for the
                   host (oracle/_ref, one core)
+  psnr_*       -- PSNR of view 0 at quarter resolution after the run (plain and EMA weights)
+  other_configs -- BASELINE configs 3, 4, 5 and the drop-in path, each in a child process of its own (one GPU, lego recipe only)
+`--dump-outputs DIR` writes what the timed path computed in its last timed step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -232,6 +237,29 @@ def measured_stream_peak(device, mbytes=1024, reps=20):
     return best
 
 
+DUMP_SAMPLE = 1 << 20      # entries kept of a tensor larger than this (a fixed, seeded choice: the same entries in every run)
+
+
+def dump_outputs(out_dir, tr, loss):
+    """--dump-outputs: what the timed path hands its caller after its last timed step, as float32 `out_dir/<name>.npy` (~14 MB in all):
+    the step's loss, every parameter of the model after the step's Adam update (the MLP weights whole, each hash-grid table as DUMP_SAMPLE
+    entries at seeded random positions, the same positions in every run), the occupancy state the next batch is marched through
+    (density_grid, density_bitfield bytes) and the sample count of the last step.  With the same arguments the inputs are the same
+    in every run (seeded scene, cameras, initialisation and ray draws), so two builds can be compared array for array."""
+    os.makedirs(out_dir, exist_ok=True)
+    model = tr.model
+    arrays = {"loss": loss.detach().float().reshape(1), "num_points": torch.tensor([float(tr.last_num_points)])}
+    for name, p in list(model.named_parameters()) + [("density_grid", model.density_grid), ("density_bitfield", model.density_bitfield)]:
+        x = p.detach().reshape(-1)
+        if x.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, x.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            x = x[idx.to(x.device)]
+            name += ".sample"
+        arrays[name] = x
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x.float().cpu().numpy())
+
+
 def dropin_reference_loop(device, steps=50, warmup=20, pretrain=300, fused_field=False, return_losses=False):
     """What a reference user gets by putting nerf2mesh_amd/backends/_*.py on sys.path and changing nothing else: the reference's OWN
     `Trainer.train_step` / `post_train_step` (nerf/utils.py:628-823) inside the loop of `train_one_epoch` (:1152-1180: occupancy refresh every
@@ -353,7 +381,7 @@ def bench_stage1(args, rank, world, device):
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         _lib.prof_reset(); _lib.prof_enable(args.prof_every)
     c0 = tr.covered_seen
     t0 = time.perf_counter()
@@ -401,7 +429,7 @@ def bench_stage1(args, rank, world, device):
                     "traffic": None, "avg_us": k["avg_us"], "algo_bytes_per_launch": k["algo_bytes_per_launch"],
                     "note": "algorithmic bytes per SURVEY.md 8d; raster operators with the measured covered-pixel count of the timed views"}
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cpu = cpu_baseline_stage1(v, f)
             except Exception as e:
@@ -517,7 +545,7 @@ def other_configs(timeout_s=180, budget_s=480):
     out = {}
     t_all = time.perf_counter()
     for name, extra in runs.items():
-        cmd = [sys.executable, me] + extra + ["--no-cpu-baseline", "--no-other-configs"]
+        cmd = [sys.executable, me] + extra + ["--full", "--no-cpu-baseline", "--no-other-configs"]
         t0 = time.perf_counter()
         if t0 - t_all > budget_s:      # the extras share ONE budget: a slow box must not push the headline line past the caller's patience
             out[name] = {"skipped": f"the extras' budget of {budget_s} s was used up by the entries before this one"}
@@ -600,7 +628,7 @@ def _main():
     ap.add_argument("--diffuse", action="store_true", help="time the reference's first-1000-iterations phase (diffuse shading: no specular branch / loss) "
                     "instead of the steady-state step")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-prof", action="store_true", help="do not record per-kernel hipEvents in the timed region")
+    ap.add_argument("--no-prof", action="store_true", help="with --full: do not record per-kernel hipEvents in the timed region")
     ap.add_argument("--prof-every", type=int, default=None, help="time every n-th launch of each kernel with hipEvents (1 = all); default "
                     "max(1, steps // 12): at least a dozen samples per kernel whatever --steps is (the driver runs 20).  The events of the step's "
                     "kernels ride on the kernel dispatches themselves (hipExtLaunchKernel start / stop events, N2M_PROF_K in csrc/n2m_common.hpp): no "
@@ -615,15 +643,21 @@ def _main():
     ap.add_argument("--num-points", type=int, default=0, help="measurement aid: override the per-step sample target (2^18 in the recipe); "
                                                                "a tiny value shows every kernel's fixed cost")
     ap.add_argument("--unfused", action="store_true", help="A/B: evaluate the MLPs with nn.Linear calls (the reference graph) instead of the fused MFMA kernels")
-    ap.add_argument("--no-other-configs", action="store_true", help="do not append `other_configs` (BASELINE configs 3, 4, 5 and the drop-in path, each "
-                    "~50 timed steps in a child process behind the headline window) and `long_run` (192 more steps) to the default line")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: do not append `other_configs` (BASELINE configs 3, 4, 5 and the drop-in "
+                    "path, each ~50 timed steps in a child process behind the headline window) and `long_run` (192 more steps) to the line")
     ap.add_argument("--dropin", action="store_true", help="time the drop-in path instead: the reference's unchanged Python over backends/_*.py (dropin_reference_loop)")
     ap.add_argument("--pipeline", action="store_true", help="BASELINE config 5 end to end on one GPU at a short schedule: --sdf stage 0 -> export_stage0 -> stage 1 -> PSNR")
     ap.add_argument("--pipeline-iters0", type=int, default=2000)
     ap.add_argument("--pipeline-iters1", type=int, default=400)
     ap.add_argument("--pipeline-resolution", type=int, default=256)
     ap.add_argument("--dropin-fused", action="store_true", help="--dropin with backends.install(fused_mlp=True): the fused MFMA field behind the unchanged NeRFNetwork")
+    ap.add_argument("--full", action="store_true", help="measure the extras as well: per-kernel events + roofline, long_run, the CPU baselines, "
+                    "PSNR, other_configs (off by default: a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last timed step computed (loss, "
+                    "parameters, occupancy grid) as DIR/<name>.npy, float32, rank 0; stage-0 step only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.stage != 0 or args.pipeline or args.dropin or args.dropin_fused):
+        ap.error("--dump-outputs writes the outputs of the stage-0 step: not with --stage 1, --pipeline or --dropin")
 
     from nerf2mesh_amd import _lib, synthetic
     from nerf2mesh_amd.network import NeRFNetwork
@@ -662,7 +696,9 @@ def _main():
             port = so.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        # a child process, not exec: this process has the HIP runtime open already (device count); it only waits for the ranks
+        import subprocess
+        sys.exit(subprocess.call(cmd))
     slack = float(os.environ.get("N2M_BENCH_TIMEOUT", "1.0"))       # multiplies every phase limit below
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         _start_watchdog()
@@ -732,13 +768,15 @@ def _main():
     if args.stage == 0 and not args.diffuse and shading != "full":
         print(f"[bench] WARNING: timed steps {first_timed}..{first_timed + args.steps - 1} run with shading={shading} "
               f"(diffuse_step={opt.diffuse_step}); raise --pretrain", file=sys.stderr)
-    if not args.no_prof:
+    prof = args.full and not args.no_prof
+    if prof:
         _lib.prof_reset()
         _lib.prof_enable(args.prof_every)       # hipEvent pairs on every n-th launch of each kernel inside the timed region
     s0, r0 = tr.samples_seen, tr.rays_seen
+    loss = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        tr.train_step()
+        loss = tr.train_step()
     barrier()
     dt = time.perf_counter() - t0
     _lib.prof_enable(False)
@@ -752,10 +790,17 @@ def _main():
         dist.all_reduce(sm, op=dist.ReduceOp.SUM)
         dt, samples, rays = float(mx[0]), float(sm[1]), float(sm[2])
 
+    if args.dump_outputs:
+        if world > 1 and hasattr(tr, "sync_parameters"):
+            tr.sync_parameters()              # (collective) complete tables on rank 0 before it writes them
+        if rank == 0:
+            dump_outputs(args.dump_outputs, tr, loss)
+        barrier()
+
     # the same step over a window that holds the occupancy refresh at exactly its long-run share (192 = 12 x 16 steps; the headline window of
     # the driver's 20 steps holds one refresh step = 5 % instead of 6.25 %): reported next to the headline, never instead of it
     long_run = None
-    if not args.no_other_configs and args.recipe == "lego" and not args.diffuse and not args.autograd:
+    if args.full and not args.no_other_configs and args.recipe == "lego" and not args.diffuse and not args.autograd:
         _lib.prof_enable(False)
         barrier()
         s1 = tr.samples_seen
@@ -785,7 +830,7 @@ def _main():
 
     kernels = {}
     side_stream = ("march_rays_train_count", "march_rays_train_write", "near_far_from_aabb") if use_engine else ()
-    if not args.no_prof:
+    if prof:
         for name in ("grid_encode_forward_packed", "grid_encode_forward", "grid_encode_backward", "grad_total_variation", "march_rays_train_count",
                      "march_rays_train_write", "composite_rays_train_forward", "composite_rays_train_backward",
                      "near_far_from_aabb", "packbits", "mlp_forward", "mlp_backward", "adam_step"):
@@ -796,11 +841,12 @@ def _main():
                                  "GBps": (by / n) / (ms / n * 1e-3) / 1e9 if ms > 0 else None,
                                  "ms_per_step": (ms / n) * seen / args.steps,                    # mean timed duration x launches per step
                                  "stream": "side (overlaps the main stream: not part of the step's critical path)" if name in side_stream else "main"}
-    try:
-        peak_measured = measured_stream_peak(device)
-    except Exception as e:
-        print(f"[bench] stream-copy peak not measured: {e!r}", file=sys.stderr)
-        peak_measured = None
+    peak_measured = None
+    if args.full:
+        try:
+            peak_measured = measured_stream_peak(device)
+        except Exception as e:
+            print(f"[bench] stream-copy peak not measured: {e!r}", file=sys.stderr)
 
     def roofline_of(name):
         k = kernels[name]
@@ -836,7 +882,7 @@ def _main():
                 r.update(achieved=None, frac=None, note="WITHDRAWN: the measured duration is implausible (events did not bracket the launch)")
 
     cpu = cpu_ref = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline()
         except Exception as e:   # the baseline is a reported extra; never lose the GPU number over it
@@ -846,13 +892,15 @@ def _main():
         except Exception as e:
             cpu_ref = {"value": None, "unit": "samples/s", "cores": 1, "kind": "reference", "sample": f"failed: {e!r}"}
 
-    try:
-        psnr = tr.eval_psnr()
-        psnr_ema = tr.eval_psnr(use_ema=True) if getattr(tr, "ema", None) is not None else None
-    except Exception as e:
-        psnr = psnr_ema = f"failed: {e!r}"
+    psnr = psnr_ema = None
+    if args.full:
+        try:
+            psnr = tr.eval_psnr()
+            psnr_ema = tr.eval_psnr(use_ema=True) if getattr(tr, "ema", None) is not None else None
+        except Exception as e:
+            psnr = psnr_ema = f"failed: {e!r}"
 
-    want_other = (world == 1 and not args.no_other_configs and args.recipe == "lego" and not args.diffuse and not args.autograd and not args.unfused
+    want_other = (args.full and world == 1 and not args.no_other_configs and args.recipe == "lego" and not args.diffuse and not args.autograd and not args.unfused
                   and args.num_points == 0)
     line = {
         "metric": "train_samples_per_sec", "value": samples / dt, "unit": "samples/s", "n_gpus": world, "steps": args.steps,

@@ -176,13 +176,13 @@ def test_a_rank_without_samples_keeps_the_collectives_in_step(shard):
 
 @pytest.mark.gpu
 def test_bench_spawns_the_ranks_it_is_asked_for():
-    """`python bench.py --gpus 2` with no launcher around it re-executes itself under torch.distributed.run: the JSON line says
+    """`python bench.py --gpus 2` with no launcher around it starts itself under torch.distributed.run: the JSON line says
     n_gpus = 2 and names the backend the ranks really used (here gloo, two ranks on the one GPU of the test box)."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(N2M_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "2", "--pretrain", "20",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-1500:]
     d = json.loads(lines[0])
@@ -232,7 +232,7 @@ def test_rccl_two_gpus_bench_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "N2M_DIST_BACKEND")}
     env.update(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--pretrain", "100",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, r.stdout[-1500:] + r.stderr[-1500:]
     d = json.loads(lines[0])

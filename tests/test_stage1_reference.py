@@ -56,8 +56,8 @@ def test_stage1_fixture_has_content():
 
 def test_stage1_fixture_is_what_the_reference_python_produces_today():
     from oracle import ref_python as RP
-    if not os.path.isdir(RP.REFERENCE):
-        pytest.skip("reference checkout not available")
+    if not RP.available():
+        pytest.skip("reference Python not available (neither the checkout nor oracle/_ref/pyref)")
     sys.path.insert(0, GOLD)
     import make_golden_stage1 as MG
     ns = RP.load("ref")

@@ -5,7 +5,7 @@ VAR=$1; A=$2; B=$3; TAG=${4:-envab}; shift 4 || true; O=gpurun_out/$TAG; mkdir -
 i=0
 for v in "$A" "$B" "$B" "$A" "$A" "$B"; do
   i=$((i+1))
-  env $VAR=$v python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs "$@" > $O/b$i.json 2>$O/b$i.err
+  env $VAR=$v python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs "$@" > $O/b$i.json 2>$O/b$i.err
   python - "$VAR=$v" $O/b$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2])); k = d["kernels"]

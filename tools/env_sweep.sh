@@ -6,7 +6,7 @@ REV=$(echo $VALS | tr ' ' '\n' | tac | tr '\n' ' ')
 i=0
 for v in $VALS $REV; do
   i=$((i+1))
-  env $VAR=$v python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs "$@" > $O/b$i.json 2>$O/b$i.err
+  env $VAR=$v python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs "$@" > $O/b$i.json 2>$O/b$i.err
   python - "$VAR=$v" $O/b$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2])); k = d["kernels"]

@@ -5,8 +5,8 @@ V=$1; TAG=${2:-libab}; O=gpurun_out/$TAG; mkdir -p $O
 i=0
 for lib in default "$V" "$V" default default "$V"; do
   i=$((i+1))
-  if [ "$lib" = default ]; then env -u N2M_HIP_LIB python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/b$i.json 2>/dev/null
-  else N2M_HIP_LIB=$(pwd)/$lib python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/b$i.json 2>/dev/null; fi
+  if [ "$lib" = default ]; then env -u N2M_HIP_LIB python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/b$i.json 2>/dev/null
+  else N2M_HIP_LIB=$(pwd)/$lib python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/b$i.json 2>/dev/null; fi
   python - "$lib" $O/b$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[2])); k = d["kernels"]

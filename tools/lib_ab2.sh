@@ -6,7 +6,7 @@ TAG=$1; shift; O=gpurun_out/$TAG; mkdir -p $O
 run() { spec=$1; i=$2
   lib=${spec%%,*}; envs=$(echo "$spec" | cut -s -d, -f2- | tr ',' ' ')
   if [ "$lib" = default ]; then e="env -u N2M_HIP_LIB $envs"; else e="env N2M_HIP_LIB=$(pwd)/$lib $envs"; fi
-  $e python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/b$i.json 2>$O/b$i.err
+  $e python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-other-configs > $O/b$i.json 2>$O/b$i.err
   python - "$spec" $O/b$i.json <<'PY'
 import json, sys
 try:
