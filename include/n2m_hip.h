@@ -483,6 +483,70 @@ int n2m_marching_cubes_emit(const float* volume, uint32_t R0, uint32_t R1, uint3
                             uint64_t workspace_bytes, double div, double mul, double add, void* vertices, int vertices_f64,
                             uint32_t cap_v, int32_t* triangles, uint32_t cap_t, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mesh decimation and midpoint subdivision   (reference: pymeshlab `meshing_decimation_quadric_edge_collapse` and
+ * `meshing_surface_subdivision_midpoint`, meshutils.py:191-231, nerf/renderer.py:209-294, :540-541, :582-583, :658-659 -- an un-vendored
+ * host library; here the passes run on the device, driven by nerf2mesh_amd/mesh_simplify.py, rule in DESIGN.md section 4.11)
+ * vertices f32 [V][3], faces i32 [F][3]; corner k of a face owns the edge (v_k, v_k+1); c2e [F][3] i32 = that edge's id; edges [E][2] i32
+ * (a < b, ascending); edge_nf [E] i32 = faces on the edge; CSR vf (vertex -> faces, ascending) and ve (vertex -> edges, ascending by the
+ * other endpoint).  flags [V] u32: bit 0 frozen, bit 1 on the boundary.  quadrics [V][10] f64.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* flags <- frozen (on an edge with > 2 faces, or on a face with face_sel[f] == 0 when face_sel != NULL) | boundary (on a 1-face edge) */
+int n2m_mesh_vertex_flags(const int32_t* faces, uint32_t F, const int32_t* c2e, const int32_t* edge_nf, const uint8_t* face_sel, uint32_t V,
+                          uint32_t* flags, void* stream);
+
+/* quadrics <- per vertex, in ascending face order: the face's area-weighted plane quadric, then boundary_weight * |e|^2 times the unit
+ * plane through each boundary edge e of the face at the vertex, perpendicular to the face */
+int n2m_mesh_quadrics(const float* vertices, uint32_t V, const int32_t* faces, const int32_t* c2e, const int32_t* edge_nf,
+                      const int32_t* vf_offsets, const int32_t* vf_faces, double boundary_weight, double* quadrics, void* stream);
+
+/* keys [E] u64 <- (f32 bits of max(cost, 0)) << 32 | mix(edge id) (a bijection of the 32-bit id, csrc/meshsimplify.hip), or ~0 for an edge that may not collapse (frozen endpoint, > 2 faces, link
+ * condition, flipped or degenerate face); placement [E][3] f32 <- the position of the surviving vertex (valid where keys != ~0) */
+int n2m_mesh_edge_collapse_cost(const float* vertices, const int32_t* faces, const int32_t* edges, const int32_t* edge_nf, uint32_t E,
+                                const uint32_t* flags, const double* quadrics, const int32_t* vf_offsets, const int32_t* vf_faces,
+                                const int32_t* ve_offsets, const int32_t* ve_edges, int optimal_placement, uint64_t* keys, float* placement,
+                                void* stream);
+
+/* selected [E] u8 <- key == min over the edges within one edge of either endpoint (an independent set: endpoints two edges apart);
+ * totals (device, 2 x u64) <- {selected edges, faces they remove}.  workspace >= 16 bytes per vertex. */
+int n2m_mesh_select_collapses(const int32_t* edges, const int32_t* edge_nf, uint32_t E, const uint64_t* keys, const int32_t* ve_offsets,
+                              const int32_t* ve_edges, uint32_t V, void* workspace, uint64_t workspace_bytes, uint8_t* selected,
+                              uint64_t* totals, void* stream);
+
+/* every selected edge (a, b): vertices[a] <- placement, quadrics[a] <- Q_a + Q_b, dest[b] <- a (dest [V] i32, -1 elsewhere); then faces are
+ * re-pointed in place and face_alive [F] u8 <- the three corners are distinct */
+int n2m_mesh_collapse_apply(const int32_t* edges, uint32_t E, const uint8_t* selected, const float* placement, float* vertices, double* quadrics,
+                            uint32_t V, int32_t* faces, uint32_t F, int32_t* dest, uint8_t* face_alive, void* stream);
+
+/* stable compaction: row i of src [n][width] (elements of 1, 4 or 8 bytes) with keep[i] -> row scan[i] - 1 of dst (scan = inclusive prefix
+ * sum of keep) */
+int n2m_mesh_compact_rows(const void* src, uint32_t n, uint32_t width, uint32_t elem_bytes, const uint8_t* keep, const int32_t* scan, void* dst,
+                          void* stream);
+
+/* referenced [V] u8 <- the vertex is a corner of some face */
+int n2m_mesh_mark_referenced(const int32_t* faces, uint32_t F, uint32_t V, uint8_t* referenced, void* stream);
+
+/* indices[i] <- scan[indices[i]] - 1 (scan = inclusive prefix sum of the kept vertices) */
+int n2m_mesh_reindex(int32_t* indices, uint32_t n, const int32_t* scan, void* stream);
+
+/* split [E] u8 <- the edge belongs to a face with face_sel != 0 and its squared length (f64) > threshold_sq */
+int n2m_mesh_subdiv_mark(const float* vertices, const int32_t* faces, uint32_t F, const int32_t* c2e, const uint8_t* face_sel, double threshold_sq,
+                         uint32_t E, uint8_t* split, void* stream);
+
+/* vertices [V + n_split][3]: row V + split_scan[e] - 1 <- f32 of the f64 midpoint of every split edge (split_scan: inclusive prefix sum) */
+int n2m_mesh_subdiv_midpoints(float* vertices, uint32_t V, const int32_t* edges, uint32_t E, const uint8_t* split, const int32_t* split_scan,
+                              void* stream);
+
+/* counts [F] i32 <- 1 + the number of split edges of the face */
+int n2m_mesh_subdiv_count(const int32_t* c2e, uint32_t F, const uint8_t* split, int32_t* counts, void* stream);
+
+/* out_faces [sum counts][3] <- the children of every face at face_scan[f] - counts[f] (face_scan: inclusive prefix sum of counts), in the
+ * order of csrc/meshsimplify.hip; out_sel (optional) <- face_sel of the parent */
+int n2m_mesh_subdiv_emit(const float* vertices, uint32_t V, const int32_t* faces, uint32_t F, const int32_t* c2e, const uint8_t* split,
+                         const int32_t* split_scan, const int32_t* face_scan, const uint8_t* face_sel, int32_t* out_faces, uint8_t* out_sel,
+                         void* stream);
+
 /* Texture-bake padding (reference: the host-side kd-tree fill of nerf/renderer.py:371-387, `NearestNeighbors(n_neighbors=1)` over texel
  * coordinates).  feats [H][W][C] u8, in place; role [H][W] u8: bit 0 = source texel (chart boundary ring), bit 1 = destination texel
  * (the band around the charts).  Every destination takes the features of the nearest source within `radius` texels (Euclidean on

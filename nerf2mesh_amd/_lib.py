@@ -84,6 +84,18 @@ SIGNATURES = {
     "n2m_marching_cubes_count": [_vp, _u32, _u32, _u32, ctypes.c_double, _vp, _u64, _vp, _vp],
     "n2m_marching_cubes_emit": [_vp, _u32, _u32, _u32, ctypes.c_double, _vp, _u64, ctypes.c_double, ctypes.c_double, ctypes.c_double, _vp, _int,
                                 _u32, _vp, _u32, _vp],
+    "n2m_mesh_vertex_flags": [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp],
+    "n2m_mesh_quadrics": [_vp, _u32, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp],
+    "n2m_mesh_edge_collapse_cost": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp],
+    "n2m_mesh_select_collapses": [_vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp],
+    "n2m_mesh_collapse_apply": [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp],
+    "n2m_mesh_compact_rows": [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp],
+    "n2m_mesh_mark_referenced": [_vp, _u32, _u32, _vp, _vp],
+    "n2m_mesh_reindex": [_vp, _u32, _vp, _vp],
+    "n2m_mesh_subdiv_mark": [_vp, _vp, _u32, _vp, _vp, ctypes.c_double, _u32, _vp, _vp],
+    "n2m_mesh_subdiv_midpoints": [_vp, _u32, _vp, _u32, _vp, _vp, _vp],
+    "n2m_mesh_subdiv_count": [_vp, _u32, _vp, _vp, _vp],
+    "n2m_mesh_subdiv_emit": [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_texture_pad_nearest": [_vp, _vp, _u32, _u32, _u32, _u32, _vp],
     "n2m_freq_encode_forward": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],

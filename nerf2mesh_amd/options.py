@@ -13,6 +13,8 @@ _DEFAULTS = dict(
     lambda_lpips=0, lambda_offsets=0.1, lambda_lap=0.001, lambda_normal=0, lambda_edgelen=0,
     contract=False, patch_size=1, trainable_density_grid=False, color_space="srgb", ind_dim=0, ind_num=500,
     ssaa=2, texture_size=4096, refine=False, gui=False,
+    refine_steps_ratio=(0.1, 0.2, 0.3, 0.4, 0.5, 0.7), refine_size=0.01, refine_decimate_ratio=0.1, refine_remesh_size=0.02,   # main.py:111-114
+    decimate_target=3e5,                                                                                                      # main.py:101
     cos_anneal_ratio=1.0, normal_anneal_epsilon=1e-4,
     fused_mlp=False,     # opt-in: fused MFMA field kernels (nerf2mesh_amd/fused.py) instead of nn.Linear calls
     enable_cam_near_far=False,     # main.py:40 (colmap mode): clamp every ray to its camera's sparse-point depth range
@@ -39,6 +41,9 @@ def make_options(**overrides):
         if o.bound > 1:
             o.contract = True
         o.enable_offset_nerf_grad = True
+        o.refine_decimate_ratio = 0                     # main.py:151-153: the SDF recipe only re-meshes
+        o.refine_size = 0
     if o.contract:                                      # main.py:155-157
         o.mark_untrained = False
+    o.refine_steps = [int(round(x * o.iters)) for x in o.refine_steps_ratio]   # main.py:181
     return o

@@ -54,6 +54,22 @@ def to_clip(vertices, mvp):
     return (vertices[:, 0:1] * m[:, 0] + vertices[:, 1:2] * m[:, 1] + vertices[:, 2:3] * m[:, 2] + m[:, 3]).contiguous()
 
 
+def percentile_linear(x, q):
+    """numpy.percentile(x, q) (method "linear") of a 1-D float tensor, on its device, in numpy's arithmetic: q / 100 and the virtual index
+    (n - 1) * q in the data's dtype, then numpy's two-sided lerp -- the threshold compares the same way numpy's does."""
+    n = x.numel()
+    s = torch.sort(x).values
+    qq = torch.tensor(float(q), dtype=x.dtype) / 100
+    vi = (n - 1) * qq
+    lo_t = torch.floor(vi)
+    g = (vi - lo_t).to(x.device)
+    lo = int(lo_t)
+    hi = min(lo + 1, n - 1)
+    a, b = s[lo], s[hi]
+    d = b - a
+    return torch.where(g >= 0.5, b - d * (1 - g), a + d * g)
+
+
 def contract(xyzs):
     mag = torch.amax(torch.abs(xyzs), dim=1, keepdim=True)
     return torch.where(mag <= 1, xyzs, xyzs * (2 - 1 / mag) / mag)
@@ -487,16 +503,20 @@ class NeRFRenderer(nn.Module):
         return vol
 
     @torch.no_grad()
-    def export_stage0(self, save_path, resolution=None, decimate_target=1e5, dataset=None, S=128):
+    def export_stage0(self, save_path, resolution=None, decimate_target=1e5, dataset=None, S=128, decimate=False):
         """Stage-0 mesh extraction (nerf/renderer.py:472-672): density volume -> marching cubes -> mesh_{cas}.ply.  The volume never leaves
         the device: the reference copies it to the host for PyMCubes (:518); here marching cubes is a HIP kernel (marching_cubes.py).
-        NOT done (pymeshlab, SURVEY section 2 OUT): clean_mesh and decimate_mesh (:535-539, :577-583, :639-646) -- the meshes written here
-        are the raw iso-surfaces (`decimate_target` is accepted for signature compatibility and ignored); the SDF recipe's contracted outer
-        shell (:548-601) is not built.  dataset: object with `.mvps [B,4,4]`, `.H`, `.W` for the visibility test, or None.
-        Returns {cascade: (vertices [V,3] f32, triangles [F,3] i32)} (device tensors)."""
+        decimate=True honours `decimate_target` where the reference does, with the device decimation of mesh_simplify.py: the inner mesh
+        after its visibility filter to `decimate_target` faces with optimal placement (:540-541), the outer cascades to
+        `decimate_target // 2` without it, before their visibility filter (:582-583, :658-659).  decimate=False (the default) writes the
+        raw iso-surfaces.  NOT done (pymeshlab, SURVEY section 2 OUT): clean_mesh (:535-539, :577-580, :639-646: merging close vertices,
+        removing floaters); the SDF recipe's contracted outer shell (:548-601) is not built.  dataset: object with `.mvps [B,4,4]`, `.H`,
+        `.W` for the visibility test, or None.  Returns {cascade: (vertices [V,3] f32, triangles [F,3] i32)} (device tensors)."""
         import os
         from . import export
         from .marching_cubes import marching_cubes
+        from .mesh_simplify import decimate as decimate_mesh
+        dec_target = int(decimate_target) if decimate and decimate_target > 0 else 0     # 0: no decimation
         os.makedirs(save_path, exist_ok=True)
         dev = self.density_bitfield.device
         if resolution is None:
@@ -517,6 +537,8 @@ class NeRFRenderer(nn.Module):
         if dataset is not None and triangles.shape[0] > 0:
             unseen = self.mark_unseen_triangles(vertices, triangles, dataset.mvps, dataset.H, dataset.W)
             vertices, triangles = export.remove_faces(vertices, triangles, unseen, dilation=getattr(self.opt, "visibility_mask_dilation", 5))
+        if dec_target and triangles.shape[0] > dec_target:
+            vertices, triangles, _ = decimate_mesh(vertices, triangles, dec_target, optimal_placement=True)
         meshes = {0: (vertices, triangles)}
         export.write_ply(os.path.join(save_path, "mesh_0.ply"), vertices.cpu().numpy(), triangles.cpu().numpy())
         if self.bound > 1 and not self.opt.sdf:
@@ -538,6 +560,8 @@ class NeRFRenderer(nn.Module):
                 v, t = export.remove_vertices(v, t, ((v <= lo) | (v >= hi)).any(dim=1))
                 if v.shape[0] == 0:
                     continue
+                if dec_target and t.shape[0] > dec_target // 2:
+                    v, t, _ = decimate_mesh(v, t, dec_target // 2, optimal_placement=False)
                 if dataset is not None and t.shape[0] > 0:
                     unseen = self.mark_unseen_triangles(v, t, dataset.mvps, dataset.H, dataset.W)
                     v, t = export.remove_faces(v, t, unseen, dilation=getattr(self.opt, "visibility_mask_dilation", 5))
@@ -546,6 +570,72 @@ class NeRFRenderer(nn.Module):
         return meshes
 
     # ------------------------------------------------------------------------------------------ stage 1
+    @torch.no_grad()
+    def refine_and_decimate(self, save_path=None):
+        """Stage-1 mesh refinement (nerf/renderer.py:209-294, meshutils.py:191-231) on the device.  The accumulated per-face errors,
+        averaged by their counts, classify the seen faces of the inner mesh: above the 90th percentile -> 2 (subdivide), below the 50th
+        -> 1 (decimate), numpy.percentile's linear rule; SDF: every face is 1.  Cascade 0 is decimated on the class-1 faces
+        (selected-only target int((1 - refine_decimate_ratio) * n1), classes carried through), then midpoint-subdivided on the class-2
+        faces at `refine_size`; the other cascades are copied and v_cumsum / f_cumsum rebuilt.  Offsets and error accumulators restart
+        at zero on the new mesh; with `save_path`, mesh_{cas}_updated.ply is written.  Returns the counts before / after, and the class-1
+        faces before ("decimate") and after the decimation ("decimate_after").
+        No seen face: the mesh is left as it is ("changed": False).
+        Differences: the isotropic re-meshing of the decimated region (`refine_remesh_size`, meshutils.py:208-209) and the non-manifold
+        repairs after it (:212-213; the device decimation keeps a manifold input manifold) are not done."""
+        from .mesh_simplify import decimate, subdivide_midpoint
+        opt = self.opt
+        dev = self.vertices.device
+        v_all = (self.vertices + self.vertices_offsets).detach().float().contiguous()
+        f_all = self.triangles.int()
+        n_inner = self.f_cumsum[1]
+        before = {"vertices": int(v_all.shape[0]), "faces": int(f_all.shape[0])}
+        err = self.triangles_errors[:n_inner].float()
+        cnt = self.triangles_errors_cnt[:n_inner].float()
+        seen = cnt > 0
+        err = torch.where(seen, err / torch.where(seen, cnt, torch.ones_like(cnt)), err)
+        if opt.sdf:
+            mask = torch.ones(n_inner, dtype=torch.uint8, device=dev)
+        else:
+            e = err[seen]
+            if e.numel() == 0:
+                return {"changed": False, "before": before, "after": before, "decimate": 0, "decimate_after": 0, "refine": 0}
+            t_ref, t_dec = percentile_linear(e, 90), percentile_linear(e, 50)
+            mask = torch.zeros(n_inner, dtype=torch.uint8, device=dev)
+            mask[(err > t_ref) & seen] = 2
+            mask[(err < t_dec) & seen] = 1
+        n_dec, n_ref = int((mask == 1).sum()), int((mask == 2).sum())
+        n_dec_after = n_dec
+        meshes = []
+        for cas in range(len(self.v_cumsum) - 1):
+            v = v_all[self.v_cumsum[cas]:self.v_cumsum[cas + 1]].contiguous()
+            f = (f_all[self.f_cumsum[cas]:self.f_cumsum[cas + 1]] - self.v_cumsum[cas]).contiguous()
+            if cas == 0:
+                if opt.refine_decimate_ratio > 0 and n_dec:
+                    v, f, src = decimate(v, f, int((1 - opt.refine_decimate_ratio) * n_dec), optimal_placement=True, selected=mask == 1)
+                    mask = mask[src]
+                    n_dec_after = int((mask == 1).sum())
+                if opt.refine_size > 0 and n_ref:
+                    v, f = subdivide_midpoint(v, f, opt.refine_size, selected=mask == 2)
+            meshes.append((v, f))
+        if save_path is not None:
+            from . import export
+            os.makedirs(save_path, exist_ok=True)
+            for cas, (v, f) in enumerate(meshes):
+                export.write_ply(os.path.join(save_path, f"mesh_{cas}_updated.ply"), v.cpu().numpy(), f.cpu().numpy())
+        v_cumsum, f_cumsum = [0], [0]
+        for v, f in meshes:
+            v_cumsum.append(v_cumsum[-1] + int(v.shape[0]))
+            f_cumsum.append(f_cumsum[-1] + int(f.shape[0]))
+        self.vertices = torch.cat([v for v, _ in meshes]).contiguous()
+        self.triangles = torch.cat([f + v0 for (_, f), v0 in zip(meshes, v_cumsum)]).to(torch.int32).contiguous()
+        self.v_cumsum, self.f_cumsum = v_cumsum, f_cumsum
+        self.vertices_offsets = nn.Parameter(torch.zeros_like(self.vertices))
+        self.triangles_errors = torch.zeros(self.triangles.shape[0], dtype=torch.float32, device=dev)
+        self.triangles_errors_cnt = torch.zeros(self.triangles.shape[0], dtype=torch.float32, device=dev)
+        self.triangles_errors_id = None
+        after = {"vertices": int(self.vertices.shape[0]), "faces": int(self.triangles.shape[0])}
+        return {"changed": True, "before": before, "after": after, "decimate": n_dec, "decimate_after": n_dec_after, "refine": n_ref}
+
     def init_stage1(self, vertices, triangles, v_cumsum=None, f_cumsum=None):
         """Attach the stage-0 mesh (what NeRFRenderer.__init__ loads from mesh_stage0/*.ply, nerf/renderer.py:123-165):
         vertices [V,3] f32, triangles [F,3] int32, learnable per-vertex offsets, per-face error accumulators."""

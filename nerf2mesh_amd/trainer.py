@@ -523,7 +523,7 @@ class Stage1Trainer:
 
     @torch.no_grad()
     def broadcast_mesh(self, src=0):
-        """After rank `src` has refined / decimated the mesh (refine_and_decimate, nerf/renderer.py:168-296: pymeshlab, outside this library) the
+        """After rank `src` has refined / decimated the mesh (NeRFRenderer.refine_and_decimate, nerf/renderer.py:209-294) the
         other ranks take its vertices and faces, re-initialise stage 1 on them and rebuild what depends on the mesh (the optimizer over
         the new vertex offsets -- nerf/utils.py:1209-1211 does the same -- and the Laplacian).  Collective."""
         if self.world <= 1:
@@ -538,10 +538,31 @@ class Stage1Trainer:
         f = model.triangles.detach().to(torch.int32).contiguous() if mine else torch.empty(nf, 3, dtype=torch.int32, device=dev)
         dist.broadcast(v, src=src)
         dist.broadcast(f, src=src)
-        step, covered, views = self.global_step, self.covered_seen, (self.view_cache, self._dirs)
-        self.__init__(model, self.opt, self.poses, v, f, dev, self.H, self.W, self.rank, self.world)      # fresh offsets, accumulators, optimizer, schedule, Laplacian
-        self.global_step, self.covered_seen = step, covered
-        self.view_cache, self._dirs = views                  # rays / ground truth / directions do not depend on the mesh
+        self._reattach(v, f)
+
+    def _reattach(self, v, f):
+        """Re-initialise stage 1 on a new mesh: fresh offsets, accumulators, optimizer, schedule and Laplacian.  The step count, the
+        covered-pixel count, the view cache (rays / ground truth / directions do not depend on the mesh) and the background generator
+        (its stream goes on, as the reference's does through a refinement) stay."""
+        keep = (self.global_step, self.covered_seen, self.view_cache, self._dirs, self.gen)
+        self.__init__(self.model, self.opt, self.poses, v, f, self.device, self.H, self.W, self.rank, self.world)
+        self.global_step, self.covered_seen, self.view_cache, self._dirs, self.gen = keep
+
+    @torch.no_grad()
+    def refine_mesh(self, src=0):
+        """The reference's stage-1 refinement step (nerf/utils.py:1204-1211): the error accumulators are summed over the ranks, rank `src`
+        refines and decimates the mesh (NeRFRenderer.refine_and_decimate), then every rank re-initialises stage 1 on the new mesh -- fresh
+        offsets, optimizer, schedule and Laplacian; the step count, the view cache and the background generator stay (_reattach).
+        Collective when world > 1.  A Stage1Engine
+        built before this call refuses to step (its mesh is gone): build a new one.  Returns refine_and_decimate's counts on rank `src`,
+        None elsewhere."""
+        self.sync_refine_state()
+        stats = self.model.refine_and_decimate() if self.rank == src else None
+        if self.world > 1:
+            self.broadcast_mesh(src)
+        else:
+            self._reattach(self.model.vertices, self.model.triangles)
+        return stats
 
     def _view(self, v):
         if v not in self.view_cache:

@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""Wall time of the device mesh passes (nerf2mesh_amd/mesh_simplify.py): decimation to 3e5 faces of the marching-cubes surfaces of a
+sphere and of "lego boxes" (a steep sigmoid of the distance to the synthetic lego stand-in's boxes, synthetic.boxes -- flat faces and sharp
+edges, not the density of a trained model) at 256^3 and 512^3, and one refine_and_decimate on a ~300 k-face mesh.  Prints one JSON object.
+
+    timeout -k 10 600 python tools/mesh_bench.py"""
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from nerf2mesh_amd import synthetic as S
+from nerf2mesh_amd.marching_cubes import marching_cubes
+from nerf2mesh_amd.mesh_simplify import decimate
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t
+
+
+def volume(kind, R):
+    g = torch.linspace(-1, 1, R, device="cuda")
+    if kind == "sphere":
+        x, y, z = torch.meshgrid(g, g, g, indexing="ij")
+        return 0.7 - torch.sqrt(x * x + y * y + z * z), 0.0
+    # "lego boxes": a steep sigmoid of the signed distance to the nearest box of the synthetic stand-in (not a trained field)
+    x, y, z = torch.meshgrid(g, g, g, indexing="ij")
+    d = torch.full_like(x, 1e9)
+    for b in S.boxes("cuda")[:, :6]:
+        q = torch.stack([(x - (b[0] + b[3]) / 2).abs() - (b[3] - b[0]) / 2, (y - (b[1] + b[4]) / 2).abs() - (b[4] - b[1]) / 2,
+                         (z - (b[2] + b[5]) / 2).abs() - (b[5] - b[2]) / 2])
+        d = torch.minimum(d, q.clamp(min=0).norm(dim=0) + q.max(0).values.clamp(max=0))
+        del q
+    return 50.0 * torch.sigmoid(-d * R), 10.0
+
+
+def main():
+    res = {"decimate": []}
+    target = 300_000
+    for kind in ("sphere", "lego boxes"):
+        for R in (256, 512):
+            vol, iso = volume(kind, R)
+            v, f = marching_cubes(vol, iso, div=R - 1.0, mul=2.0, add=-1.0)
+            del vol
+            decimate(v, f, target)                          # warm-up (kernels loaded, allocator primed)
+            stats = {}
+            (dv, df, _), sec = timed(lambda: decimate(v, f, target, stats=stats))
+            res["decimate"].append({"mesh": kind, "reso": R, "faces_in": int(f.shape[0]), "faces_out": int(df.shape[0]), "seconds": round(sec, 4),
+                                    "rounds": stats["rounds"], "faces_per_round": stats["faces"]})
+            print(json.dumps(res["decimate"][-1]), file=sys.stderr, flush=True)
+    # one refine_and_decimate on a ~300 k-face mesh with a random error field
+    from nerf2mesh_amd.network import NeRFNetwork
+    from nerf2mesh_amd.options import make_options
+    torch.manual_seed(0)
+    v, f = S.scene_mesh(300_000)
+    model = NeRFNetwork(make_options(O=True, bound=1, dt_gamma=0, stage=1)).cuda()
+    model.init_stage1(v, f)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    model.triangles_errors.copy_(torch.rand(f.shape[0], device="cuda", generator=g))
+    model.triangles_errors_cnt.fill_(1)
+    out, sec = timed(lambda: model.refine_and_decimate())
+    res["refine_and_decimate"] = {"faces_in": out["before"]["faces"], "faces_out": out["after"]["faces"], "seconds": round(sec, 4),
+                                  "decimate_class": out["decimate"], "refine_class": out["refine"]}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
