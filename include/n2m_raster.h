@@ -50,12 +50,14 @@ int n2m_interpolate_backward_strided(const float* attr, const float* rast, const
                                      void* stream);
 
 /* Edge -> opposite-vertex hash used by antialias.  table: [capacity] entries of 4 x i32 (va, vb, op0, op1), capacity a
- * power of two >= 4*F (caller allocates 16*capacity bytes; contents are overwritten). */
+ * power of two >= 4*F (caller allocates 16*capacity bytes; contents are overwritten).  An edge with more than two faces keeps
+ * op1 = -2: it has no single neighbour, and antialias treats it as a silhouette for every incident face, so the result does
+ * not depend on the order of the faces or of the table's construction. */
 int n2m_antialias_build_topology(const int32_t* tri, uint32_t F, int32_t* table, uint32_t capacity, void* stream);
 
 /* dr.antialias.  color [H,W,C] f32 -> out [H,W,C]: for every horizontally / vertically adjacent pixel pair whose
- * triangle ids differ, the nearer surface's triangle is examined; if one of its SILHOUETTE edges (boundary edge, or the
- * two adjacent triangles lie on the same screen-space side) crosses the segment joining the two pixel centres at
+ * triangle ids differ, the nearer surface's triangle is examined; if one of its SILHOUETTE edges (boundary edge, edge with
+ * more than two faces, or the two adjacent triangles lie on the same screen-space side) crosses the segment joining the two pixel centres at
  * fraction d (measured from the covered pixel), the pixel on the far side of the midpoint is blended toward its
  * neighbour by |0.5 - d|. */
 int n2m_antialias_forward(const float* color, const float* rast, const float* pos, const int32_t* tri,

@@ -387,6 +387,7 @@ __global__ void interpolate_backward_kernel(const float* __restrict__ attr, cons
 
 // -------------------------------------------------------------------------------------------------- antialias
 struct Edge { unsigned long long key; int32_t op0, op1; };   // 16 bytes = 4 x i32 (va, vb, op0, op1)
+constexpr int32_t kManyFaces = -2;     // op1 of an edge with more than two faces: a silhouette for every one of them
 
 __device__ __forceinline__ uint32_t edge_hash(uint32_t a, uint32_t b) {
     uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA6Bu;
@@ -411,7 +412,9 @@ __global__ void topology_insert_kernel(const int32_t* __restrict__ tri, uint32_t
     for (uint32_t probe = 0; probe < capacity; ++probe, slot = (slot + 1) & (capacity - 1)) {
         const unsigned long long old = atomicCAS(&table[slot].key, ~0ull, key);
         if (old == ~0ull || old == key) {
-            if (atomicCAS(&table[slot].op0, -1, c) != -1) atomicCAS(&table[slot].op1, -1, c);
+            // the first two faces fill op0 / op1; any further face finds both taken and marks the edge.  Which two faces won is a
+            // matter of thread timing, so a third face must not leave a pair behind that the lookup could trust
+            if (atomicCAS(&table[slot].op0, -1, c) != -1 && atomicCAS(&table[slot].op1, -1, c) != -1) atomicExch(&table[slot].op1, kManyFaces);
             return;
         }
     }
@@ -423,7 +426,11 @@ __device__ __forceinline__ int topology_other(const Edge* __restrict__ table, ui
     uint32_t slot = edge_hash(lo, hi) & (capacity - 1);
     for (uint32_t probe = 0; probe < capacity; ++probe, slot = (slot + 1) & (capacity - 1)) {
         const unsigned long long k = table[slot].key;
-        if (k == key) { const int32_t o0 = table[slot].op0, o1 = table[slot].op1; return o0 != c ? o0 : o1; }
+        if (k == key) {
+            const int32_t o0 = table[slot].op0, o1 = table[slot].op1;
+            if (o1 == kManyFaces) return -1;                    // non-manifold edge: no single neighbour, a silhouette like a boundary
+            return o0 != c ? o0 : o1;
+        }
         if (k == ~0ull) return -1;
     }
     return -1;

@@ -85,6 +85,8 @@ class _interpolate(Function):
         rast = rast.float().contiguous()
         B, H, W = rast.shape[0], rast.shape[1], rast.shape[2]
         Ba, V, A = attr.shape
+        if Ba not in (1, B):
+            raise ValueError(f"attr minibatch {Ba} must be 1 (broadcast) or the rast minibatch {B}")
         out = torch.empty(B, H, W, A, dtype=torch.float32, device=rast.device)
         for b in range(B):
             L.call("n2m_interpolate_forward", _p(attr[b if Ba > 1 else 0]), _p(rast[b]), _p(tri), V, tri.shape[0], A, H, W, _p(out[b]),

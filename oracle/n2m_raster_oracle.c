@@ -165,13 +165,14 @@ static int other_vertex(const edge_t* e, size_t n, int32_t a, int32_t b, int32_t
     const int32_t lo = a < b ? a : b, hi = a < b ? b : a;
     size_t l = 0, r = n;
     while (l < r) { const size_t m = (l + r) / 2; if (e[m].lo < lo || (e[m].lo == lo && e[m].hi < hi)) l = m + 1; else r = m; }
-    /* entries of this edge are consecutive; return an opposite vertex different from c (first two only, like the product) */
+    /* entries of this edge are consecutive; return an opposite vertex different from c */
     int first = -1, second = -1, cnt = 0;
     for (size_t i = l; i < n && e[i].lo == lo && e[i].hi == hi; ++i) { if (cnt == 0) first = e[i].op; else if (cnt == 1) second = e[i].op; ++cnt; }
     if (cnt == 0) return -1;
     if (cnt == 1) return first != c ? first : -1;
-    /* two (or more) triangles share the edge: the one that is not c; insertion order in the product's table is not
-       defined, so a non-manifold edge (cnt > 2) is ambiguous there as well */
+    /* more than two triangles on the edge (non-manifold): no single neighbour, so -1 -- a silhouette for every one of them, whatever
+       the order of the faces */
+    if (cnt > 2) return -1;
     return first != c ? first : second;
 }
 
