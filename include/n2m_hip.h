@@ -547,6 +547,63 @@ int n2m_mesh_subdiv_emit(const float* vertices, uint32_t V, const int32_t* faces
                          const int32_t* split_scan, const int32_t* face_scan, const uint8_t* face_sel, int32_t* out_faces, uint8_t* out_sel,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * mesh cleaning   (reference: pymeshlab `clean_mesh`, meshutils.py:146-188, nerf/renderer.py:537, :653 -- merge close vertices,
+ * duplicate / null faces, small components, non-manifold edges and vertices; driven by nerf2mesh_amd/mesh_clean.py, rule in DESIGN.md
+ * section 4.12).  Same mesh layout as above; totals are device u64 counters, zeroed by the call.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* keys [V] i64 <- (cx * ny + cy) * nz + cz, c = floor((p - lo) / cell) per axis in f64, clamped to [0, n - 1] */
+int n2m_mesh_clean_cell_keys(const float* vertices, uint32_t V, double lo_x, double lo_y, double lo_z, double cell, int32_t nx, int32_t ny,
+                             int32_t nz, int64_t* keys, void* stream);
+
+/* one round of the vertex merge: state_out <- state_in advanced by one round (-1 undecided, v seed, s < v mapped to seed s) over the
+ * neighbours closer than sqrt(r2) found in the 27 cells around each vertex; order [V] = vertex ids sorted by key, cell_offsets
+ * [nx ny nz + 1] = their CSR offsets; blocker [V] i32 (-1 at the start) is carried between rounds; undecided (device u32) <- the count
+ * still undecided */
+int n2m_mesh_clean_merge_round(const float* vertices, uint32_t V, const int32_t* order, const int64_t* keys, const int32_t* cell_offsets,
+                               int32_t nx, int32_t ny, int32_t nz, double r2, const int32_t* state_in, int32_t* state_out, int32_t* blocker,
+                               uint32_t* undecided, void* stream);
+
+/* faces[i] <- dest[faces[i]] in place; face_alive [F] u8 <- the three corners are distinct */
+int n2m_mesh_clean_repoint(int32_t* faces, uint32_t F, const int32_t* dest, uint8_t* face_alive, void* stream);
+
+/* order [F]: face ids sorted by sorted corner triple, ties ascending.  face_alive <- first of its triple and a nonzero f64 cross product;
+ * totals (2 x u64) <- {duplicates, null faces} */
+int n2m_mesh_clean_dup_null(const float* vertices, const int32_t* faces, uint32_t F, const int32_t* order, uint8_t* face_alive, uint64_t* totals,
+                            void* stream);
+
+/* edge-connected components by union-find: label [F] i32 <- the smallest face id of the component; the workspace (>= 4 E + 32 F bytes)
+ * keeps the per-component face counts and boxes for n2m_mesh_clean_component_filter */
+int n2m_mesh_clean_components(const float* vertices, const int32_t* faces, uint32_t F, const int32_t* c2e, uint32_t E, void* workspace,
+                              uint64_t workspace_bytes, int32_t* label, void* stream);
+
+/* face_alive <- the component's box diagonal (f64) >= min_diameter (if use_diameter) and then its face count >= min_faces (if > 0);
+ * totals (5 x u64) <- {components, removed by diameter: components, faces; removed by face count: components, faces} */
+int n2m_mesh_clean_component_filter(uint32_t F, const int32_t* label, const void* workspace, uint32_t E, int use_diameter, double min_diameter,
+                                    int32_t min_faces, uint8_t* face_alive, uint64_t* totals, void* stream);
+
+/* double_area [F] f64 <- |(b - a) x (c - a)|; state [F] u8 <- 0 for a face on an edge with > 2 faces (candidate), else 1;
+ * totals (1 x u64) <- candidates */
+int n2m_mesh_clean_nm_edge_init(const float* vertices, const int32_t* faces, uint32_t F, const int32_t* c2e, const int32_t* edge_nf,
+                                double* double_area, uint8_t* state, uint64_t* totals, void* stream);
+
+/* one round of the non-manifold-edge deletion in (double area, id) order: state_out <- state_in with the candidates decided whose smaller
+ * candidates on their non-manifold edges are decided (1 kept, 2 deleted); ef_offsets / ef_faces: edge -> faces CSR; totals (2 x u64) <-
+ * {still undecided, deleted in this round} */
+int n2m_mesh_clean_nm_edge_round(uint32_t F, const int32_t* c2e, const int32_t* edge_nf, const int32_t* ef_offsets, const int32_t* ef_faces,
+                                 const double* double_area, const uint8_t* state_in, uint8_t* state_out, uint64_t* totals, void* stream);
+
+/* vf_offsets [V + 1] / vf_corners [3F]: vertex -> flat corner ids, ascending.  visited [3F] u8 <- the corner is in the fan of its vertex's
+ * first corner (stack [3F] i32: scratch); split [V] u8 <- the vertex has more than one fan; first_corner [V] i32 <- its first corner
+ * (INT32_MAX if unreferenced); totals (1 x u64) <- split vertices */
+int n2m_mesh_clean_fan_walk(const int32_t* faces, uint32_t F, uint32_t V, const int32_t* vf_offsets, const int32_t* vf_corners, uint8_t* visited,
+                            int32_t* stack, uint8_t* split, int32_t* first_corner, uint64_t* totals, void* stream);
+
+/* vertices [V + n_split][3]: row V + r <- row split_ids[r], and the corners of that vertex's first fan (visited) are re-pointed to V + r */
+int n2m_mesh_clean_fan_split(float* vertices, uint32_t V, int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners,
+                             const uint8_t* visited, const int32_t* split_ids, uint32_t n_split, void* stream);
+
 /* Texture-bake padding (reference: the host-side kd-tree fill of nerf/renderer.py:371-387, `NearestNeighbors(n_neighbors=1)` over texel
  * coordinates).  feats [H][W][C] u8, in place; role [H][W] u8: bit 0 = source texel (chart boundary ring), bit 1 = destination texel
  * (the band around the charts).  Every destination takes the features of the nearest source within `radius` texels (Euclidean on

@@ -96,6 +96,16 @@ SIGNATURES = {
     "n2m_mesh_subdiv_midpoints": [_vp, _u32, _vp, _u32, _vp, _vp, _vp],
     "n2m_mesh_subdiv_count": [_vp, _u32, _vp, _vp, _vp],
     "n2m_mesh_subdiv_emit": [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_clean_cell_keys": [_vp, _u32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i32, _i32, _i32, _vp, _vp],
+    "n2m_mesh_clean_merge_round": [_vp, _u32, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_clean_repoint": [_vp, _u32, _vp, _vp, _vp],
+    "n2m_mesh_clean_dup_null": [_vp, _vp, _u32, _vp, _vp, _vp, _vp],
+    "n2m_mesh_clean_components": [_vp, _vp, _u32, _vp, _u32, _vp, _u64, _vp, _vp],
+    "n2m_mesh_clean_component_filter": [_u32, _vp, _vp, _u32, _int, ctypes.c_double, _i32, _vp, _vp, _vp],
+    "n2m_mesh_clean_nm_edge_init": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_clean_nm_edge_round": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_clean_fan_walk": [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_clean_fan_split": [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "n2m_texture_pad_nearest": [_vp, _vp, _u32, _u32, _u32, _u32, _vp],
     "n2m_freq_encode_forward": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],

@@ -126,7 +126,7 @@ def write_mlp_json(path, model):
 
 # ------------------------------------------------------------------------------------------------ mesh filters
 # The two pymeshlab selections export_stage0 uses between marching cubes and the PLY (meshutils.py:63-143), on device tensors.
-# (clean_mesh / decimate_mesh, meshutils.py:27-60,146-190, are CPU mesh post-processing through pymeshlab: out of scope)
+# (clean_mesh and decimate_mesh, meshutils.py:27-60,146-190, run on the device too: mesh_clean.clean_mesh, mesh_simplify.decimate.)
 
 def remove_vertices(vertices, triangles, selected):
     """Deletes the selected vertices and every face that touches one (`meshing_remove_selected_vertices`, meshutils.py:122-143);

@@ -15,6 +15,7 @@ _DEFAULTS = dict(
     ssaa=2, texture_size=4096, refine=False, gui=False,
     refine_steps_ratio=(0.1, 0.2, 0.3, 0.4, 0.5, 0.7), refine_size=0.01, refine_decimate_ratio=0.1, refine_remesh_size=0.02,   # main.py:111-114
     decimate_target=3e5,                                                                                                      # main.py:101
+    clean_min_f=8, clean_min_d=5,                                                                                             # main.py:104-105
     cos_anneal_ratio=1.0, normal_anneal_epsilon=1e-4,
     fused_mlp=False,     # opt-in: fused MFMA field kernels (nerf2mesh_amd/fused.py) instead of nn.Linear calls
     enable_cam_near_far=False,     # main.py:40 (colmap mode): clamp every ray to its camera's sparse-point depth range

@@ -503,18 +503,22 @@ class NeRFRenderer(nn.Module):
         return vol
 
     @torch.no_grad()
-    def export_stage0(self, save_path, resolution=None, decimate_target=1e5, dataset=None, S=128, decimate=False):
+    def export_stage0(self, save_path, resolution=None, decimate_target=1e5, dataset=None, S=128, decimate=False, clean=False):
         """Stage-0 mesh extraction (nerf/renderer.py:472-672): density volume -> marching cubes -> mesh_{cas}.ply.  The volume never leaves
         the device: the reference copies it to the host for PyMCubes (:518); here marching cubes is a HIP kernel (marching_cubes.py).
-        decimate=True honours `decimate_target` where the reference does, with the device decimation of mesh_simplify.py: the inner mesh
-        after its visibility filter to `decimate_target` faces with optimal placement (:540-541), the outer cascades to
-        `decimate_target // 2` without it, before their visibility filter (:582-583, :658-659).  decimate=False (the default) writes the
-        raw iso-surfaces.  NOT done (pymeshlab, SURVEY section 2 OUT): clean_mesh (:535-539, :577-580, :639-646: merging close vertices,
-        removing floaters); the SDF recipe's contracted outer shell (:548-601) is not built.  dataset: object with `.mvps [B,4,4]`, `.H`,
-        `.W` for the visibility test, or None.  Returns {cascade: (vertices [V,3] f32, triangles [F,3] i32)} (device tensors)."""
+        clean=True runs the device clean_mesh of mesh_clean.py where the reference runs pymeshlab's (merging close vertices, removing
+        duplicate / null faces and floaters, repairing non-manifold geometry): on the inner mesh after its visibility filter with
+        repair=True (:537), on each outer cascade after the out-of-AABB removal with repair=False, skipping a cascade it empties
+        (:653-655); min_f / min_d are opt.clean_min_f / clean_min_d.  decimate=True honours `decimate_target` where the reference does,
+        with the device decimation of mesh_simplify.py: the inner mesh after its visibility filter (and cleaning) to `decimate_target` faces
+        with optimal placement (:540-541), the outer cascades to `decimate_target // 2` without it, before their visibility filter
+        (:582-583, :658-659).  With neither (the default) the raw iso-surfaces are written.  NOT done: the SDF recipe's contracted outer
+        shell (:548-601).  dataset: object with `.mvps [B,4,4]`, `.H`, `.W` for the visibility test, or None.
+        Returns {cascade: (vertices [V,3] f32, triangles [F,3] i32)} (device tensors)."""
         import os
         from . import export
         from .marching_cubes import marching_cubes
+        from .mesh_clean import clean_mesh
         from .mesh_simplify import decimate as decimate_mesh
         dec_target = int(decimate_target) if decimate and decimate_target > 0 else 0     # 0: no decimation
         os.makedirs(save_path, exist_ok=True)
@@ -537,6 +541,8 @@ class NeRFRenderer(nn.Module):
         if dataset is not None and triangles.shape[0] > 0:
             unseen = self.mark_unseen_triangles(vertices, triangles, dataset.mvps, dataset.H, dataset.W)
             vertices, triangles = export.remove_faces(vertices, triangles, unseen, dilation=getattr(self.opt, "visibility_mask_dilation", 5))
+        if clean:
+            vertices, triangles, _ = clean_mesh(vertices, triangles, min_f=self.opt.clean_min_f, min_d=self.opt.clean_min_d, repair=True)
         if dec_target and triangles.shape[0] > dec_target:
             vertices, triangles, _ = decimate_mesh(vertices, triangles, dec_target, optimal_placement=True)
         meshes = {0: (vertices, triangles)}
@@ -560,6 +566,10 @@ class NeRFRenderer(nn.Module):
                 v, t = export.remove_vertices(v, t, ((v <= lo) | (v >= hi)).any(dim=1))
                 if v.shape[0] == 0:
                     continue
+                if clean:
+                    v, t, _ = clean_mesh(v, t, min_f=self.opt.clean_min_f, min_d=self.opt.clean_min_d, repair=False)
+                    if v.shape[0] == 0:
+                        continue
                 if dec_target and t.shape[0] > dec_target // 2:
                     v, t, _ = decimate_mesh(v, t, dec_target // 2, optimal_placement=False)
                 if dataset is not None and t.shape[0] > 0:
