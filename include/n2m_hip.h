@@ -604,6 +604,56 @@ int n2m_mesh_clean_fan_walk(const int32_t* faces, uint32_t F, uint32_t V, const 
 int n2m_mesh_clean_fan_split(float* vertices, uint32_t V, int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_corners,
                              const uint8_t* visited, const int32_t* split_ids, uint32_t n_split, void* stream);
 
+/* UV atlas (csrc/uvatlas.hip; the rule: DESIGN.md section 4.13; driver: nerf2mesh_amd/uv_atlas.py).  Directions k = 2 * axis + (sign < 0).
+ * c2e / edge_nf as above; every fp64 value is computed from the fp32 inputs in a fixed operand order.
+ *
+ * normal [F][3] f64 <- (b - a) x (c - a), double_area [F] f64 <- its length, edge_length [F][3] f64 <- |v_k+1 - v_k|, label [F] i32 <-
+ * argmax_k normal . d_k (ties: lowest k); totals (1 x u64) <- faces with a repeated corner or a zero normal */
+int n2m_uv_face_frames(const float* vertices, const int32_t* faces, uint32_t F, double* normal, double* double_area, double* edge_length,
+                       int32_t* label, uint64_t* totals, void* stream);
+
+/* edge_min_face / edge_max_face [E] i32 <- the smallest / largest face id on the edge */
+int n2m_uv_edge_faces(const int32_t* c2e, uint32_t F, uint32_t E, int32_t* edge_min_face, int32_t* edge_max_face, void* stream);
+
+/* one Jacobi relaxation round: label_out [F] from label_in [F] (different buffers); changed (1 x u64) <- faces whose label changed */
+int n2m_uv_relax_round(uint32_t F, const int32_t* c2e, const int32_t* edge_nf, const int32_t* edge_min_face, const int32_t* edge_max_face,
+                       const double* edge_length, const double* normal, const double* double_area, double min_cos, const int32_t* label_in,
+                       int32_t* label_out, uint64_t* changed, void* stream);
+
+/* charts: union-find over the edges with exactly two faces of equal label and equal generation.  parent [F] i32: scratch; root [F] i32 <-
+ * the chart's smallest face id; is_root [F] u8 <- the face is that face */
+int n2m_uv_charts(uint32_t F, const int32_t* c2e, const int32_t* edge_nf, const int32_t* edge_min_face, const int32_t* edge_max_face,
+                  const int32_t* label, const int32_t* generation, int32_t* parent, int32_t* root, uint8_t* is_root, void* stream);
+
+/* projected [T][2] f32 <- the UV vertex's mesh vertex on the two axes of its chart's direction; chart_box [C][4] u32 <- the charts' boxes
+ * (min u, min v, max u, max v) in the order-preserving integer encoding of floats */
+int n2m_uv_project(const float* vertices, const int32_t* vmapping, const int32_t* vertex_chart, const int32_t* chart_label, uint32_t T, uint32_t C,
+                   float* projected, uint32_t* chart_box, void* stream);
+
+/* sum (1 x f64) <- the sum of values [n] in one fixed order: 256 strided partials, each left to right, then added left to right */
+int n2m_uv_sum_f64(const double* values, uint32_t n, double* sum, void* stream);
+
+/* rect [C][2] i32 <- (width, height) = min(ceil(scale * extent), 2^30) + 1 + 2 * gutter; sort_key [C] i64 <- -(height * 2^32 + width) */
+int n2m_uv_rects(const uint32_t* chart_box, uint32_t C, double scale, int32_t gutter, int32_t* rect, int64_t* sort_key, void* stream);
+
+/* shelf packing of the rectangles in `order` [C] i32, left to right, a new shelf when the row is full: origin [C][2] i32 <- (x, y);
+ * result (2 x i32) <- {every rectangle fits in width and the shelves in height, the height used} */
+int n2m_uv_shelf_pack(const int32_t* rect, const int32_t* order, uint32_t C, int32_t height, int32_t width, int32_t* origin, int32_t* result,
+                      void* stream);
+
+/* vt [T][2] f32 <- ((origin + gutter + 0.5) + scale * (projected - chart min)) / (width, height) */
+int n2m_uv_write_vt(const float* projected, const int32_t* vertex_chart, const uint32_t* chart_box, const int32_t* origin, uint32_t T, double scale,
+                    int32_t gutter, int32_t height, int32_t width, float* vt, void* stream);
+
+/* canvas [height][width] i32 <- per texel the smallest face whose UV triangle holds the texel centre strictly inside (INT-like 0x7f7f7f7f:
+ * none); evicted [F] u8 <- some interior texel of the face holds a smaller face id */
+int n2m_uv_canvas_evict(const float* vt, const int32_t* ft, uint32_t F, int32_t height, int32_t width, int32_t* canvas, uint8_t* evicted,
+                        void* stream);
+
+/* texel_area [F] f64 <- the signed UV area in texels; density [F] f64 <- texel_area / (double_area / 2) */
+int n2m_uv_face_metrics(const float* vt, const int32_t* ft, const double* double_area, uint32_t F, int32_t height, int32_t width, double* texel_area,
+                        double* density, void* stream);
+
 /* Texture-bake padding (reference: the host-side kd-tree fill of nerf/renderer.py:371-387, `NearestNeighbors(n_neighbors=1)` over texel
  * coordinates).  feats [H][W][C] u8, in place; role [H][W] u8: bit 0 = source texel (chart boundary ring), bit 1 = destination texel
  * (the band around the charts).  Every destination takes the features of the nearest source within `radius` texels (Euclidean on

@@ -106,6 +106,17 @@ SIGNATURES = {
     "n2m_mesh_clean_nm_edge_round": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_mesh_clean_fan_walk": [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_mesh_clean_fan_split": [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "n2m_uv_face_frames": [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_uv_edge_faces": [_vp, _u32, _u32, _vp, _vp, _vp],
+    "n2m_uv_relax_round": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp, _vp],
+    "n2m_uv_charts": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_uv_project": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
+    "n2m_uv_sum_f64": [_vp, _u32, _vp, _vp],
+    "n2m_uv_rects": [_vp, _u32, ctypes.c_double, _i32, _vp, _vp, _vp],
+    "n2m_uv_shelf_pack": [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp],
+    "n2m_uv_write_vt": [_vp, _vp, _vp, _vp, _u32, ctypes.c_double, _i32, _i32, _i32, _vp, _vp],
+    "n2m_uv_canvas_evict": [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp],
+    "n2m_uv_face_metrics": [_vp, _vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp],
     "n2m_texture_pad_nearest": [_vp, _vp, _u32, _u32, _u32, _u32, _vp],
     "n2m_freq_encode_forward": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],

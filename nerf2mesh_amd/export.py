@@ -8,8 +8,8 @@
   `bound` and `cascade` (nerf/renderer.py:452-468), consumed by renderer.html:424-472.
 
 Marching cubes, mesh cleaning/decimation (PyMCubes, pymeshlab) and UV unwrapping (xatlas) are host-side third-party steps of the
-reference's export path (nerf/renderer.py:298-672) and are out of this package's scope (OUT rows); the writers
-here take their results as arrays.
+reference's export path (nerf/renderer.py:298-672); the package builds its own device versions (marching_cubes.py, mesh_clean.py,
+mesh_simplify.py, uv_atlas.py: DESIGN 4.9, 4.11-4.13) and the writers here take their results as arrays.
 """
 import json
 import os
@@ -159,8 +159,8 @@ def remove_faces(vertices, triangles, remove, dilation=5):
 def grid_atlas(n_faces, margin=0.12, device="cpu"):
     """A trivial UV atlas: face i gets its own right triangle in cell i // 2 of a G x G grid (two faces per cell, `margin` of the cell
     kept free around each).  Returns (vt [3 F, 2] in [0, 1], ft [F, 3] int32).  Stand-in for the xatlas unwrap of nerf/renderer.py:312-322
-    (xatlas is an un-vendored dependency and UV unwrapping is outside the hot path): valid and seam-free per face,
-    but it spends the texture uniformly per face instead of per area."""
+    (xatlas is an un-vendored dependency): valid and seam-free per face, but it spends the texture uniformly per face instead of per
+    area.  uv_atlas.uv_atlas (export_stage1(..., atlas="charts")) is the area-proportional chart atlas built on the device."""
     import math
     import torch
     F = int(n_faces)

@@ -716,11 +716,18 @@ class NeRFRenderer(nn.Module):
     @torch.no_grad()
     def export_stage1(self, path, h0=2048, w0=2048, atlas=None):
         """nerf/renderer.py:298-468: per cascade `mesh_{cas}.obj/.mtl`, `feat0_{cas}.jpg` (diffuse), `feat1_{cas}.jpg` (specular
-        features), and `mlp.json` -- the files renderer.html loads.  atlas: {cas: (vt [T,2] in [0,1], ft [F,3])}; the reference unwraps
-        with xatlas (:312-322, un-vendored, outside the hot path) -- without an atlas every face gets its own cell (export.grid_atlas)."""
+        features), and `mlp.json` -- the files renderer.html loads.  atlas: {cas: (vt [T,2] in [0,1], ft [F,3])}, or "charts": every
+        cascade is unwrapped on the device by uv_atlas.uv_atlas at its own (h0 * ssaa, w0 * ssaa) -- of contract(v) when opt.contract is
+        set, as the reference's xatlas call sees it (:312-322) --; None: every face gets its own cell (export.grid_atlas, the stand-in).
+        self.last_atlas keeps {cas: (vt, ft, vmapping-or-None)} of the call."""
         import os
         from . import export
         assert self.opt.stage > 0, "export_stage1 needs the stage-1 mesh (init_stage1)"
+        if isinstance(atlas, str):
+            if atlas != "charts":
+                raise ValueError(f"export_stage1: atlas must be None, a dict or \"charts\", got {atlas!r}")
+            from .uv_atlas import uv_atlas
+        self.last_atlas = {}
         os.makedirs(path, exist_ok=True)
         v_all = (self.vertices + self.vertices_offsets).detach()
         f_all = self.triangles.detach()
@@ -730,13 +737,18 @@ class NeRFRenderer(nn.Module):
             v = v_all[self.v_cumsum[cas]:self.v_cumsum[cas + 1]].contiguous()
             f = (f_all[self.f_cumsum[cas]:self.f_cumsum[cas + 1]] - self.v_cumsum[cas]).contiguous()
             if f.shape[0] > 0:       # (an empty cascade writes nothing but still takes part in the halving below, nerf/renderer.py:440-448)
-                vt, ft = atlas[cas] if atlas is not None else export.grid_atlas(f.shape[0], device=v.device)
+                vmapping = None
+                if isinstance(atlas, str):
+                    vt, ft, vmapping = uv_atlas(contract(v) if self.opt.contract else v, f, int(h0 * ssaa), int(w0 * ssaa))
+                else:
+                    vt, ft = atlas[cas] if atlas is not None else export.grid_atlas(f.shape[0], device=v.device)
                 vt, ft = torch.as_tensor(vt).float().to(v.device), torch.as_tensor(ft).int().to(v.device)
                 feat0, feat1, mask = self.bake_textures(v, f, vt, ft, h0, w0, ssaa)
                 export.write_jpg(os.path.join(path, f"feat0_{cas}.jpg"), feat0.cpu().numpy())
                 export.write_jpg(os.path.join(path, f"feat1_{cas}.jpg"), feat1.cpu().numpy())
                 export.write_obj(path, cas, v.cpu().numpy(), f.cpu().numpy(), vt.cpu().numpy(), ft.cpu().numpy())
                 out[cas] = (feat0, feat1, mask)
+                self.last_atlas[cas] = (vt, ft, vmapping)
             if not self.opt.sdf and h0 > 2048 and w0 > 2048:      # half the texture resolution for the remote cascades (:446-448)
                 h0 //= 2
                 w0 //= 2
