@@ -547,6 +547,48 @@ int n2m_mesh_subdiv_emit(const float* vertices, uint32_t V, const int32_t* faces
                          const int32_t* split_scan, const int32_t* face_scan, const uint8_t* face_sel, int32_t* out_faces, uint8_t* out_sel,
                          void* stream);
 
+/* ---- isotropic re-meshing (csrc/meshremesh.hip): the passes 4.11's entry points do not already have.  Mesh layout as above;
+ * edge_corners [3F] i32 = the corner ids 3 f + k sorted (stably) by the edge the corner owns, edge_offsets [E + 1] i32 its offsets. */
+
+/* split [E] u8 <- the edge's squared length (f64) > threshold_sq and every face on it has face_sel != 0 */
+int n2m_mesh_remesh_split_mark(const float* vertices, const int32_t* edges, uint32_t E, uint32_t F, const int32_t* c2e, const uint8_t* face_sel,
+                               double threshold_sq, uint8_t* split, void* stream);
+
+/* edge_feature [E] u8 <- the edge has one face, more than two, or n0 . n1 < cos_feature |n0| |n1|.  vertex_class [V] u32 <- flags (of
+ * n2m_mesh_vertex_flags: 1 frozen, 2 boundary) | 4 with two feature edges that go on straight within the feature angle | 1 (a corner)
+ * with one, more than two, or two that turn by more than it */
+int n2m_mesh_remesh_classify(const float* vertices, uint32_t V, const int32_t* faces, const int32_t* edges, uint32_t E, const int32_t* edge_offsets,
+                             const int32_t* edge_corners, const int32_t* ve_offsets, const int32_t* ve_edges, const uint32_t* flags,
+                             double cos_feature, uint8_t* edge_feature, uint32_t* vertex_class, void* stream);
+
+/* keys [E] u64 <- fp32 bits of the squared length << 32 | mix(e) for the edges shorter than sqrt(lo_sq) whose collapse is valid (no frozen
+ * endpoint, two feature vertices only along a feature edge, link condition, no face turned against its old normal or its vertex's normal, no new edge longer than sqrt(hi_sq)), ~0
+ * otherwise; placement [E][3] <- the midpoint, or the one endpoint that is a feature vertex.  For n2m_mesh_select_collapses. */
+int n2m_mesh_remesh_collapse_cost(const float* vertices, const int32_t* faces, const int32_t* edges, const int32_t* edge_nf, uint32_t E,
+                                  const uint32_t* vertex_class, const uint8_t* edge_feature, const int32_t* vf_offsets, const int32_t* vf_faces,
+                                  const int32_t* ve_offsets, const int32_t* ve_edges, double lo_sq, double hi_sq, uint64_t* keys, float* placement,
+                                  void* stream);
+
+/* One round of edge flips towards valence 6 (4 on a boundary): candidates, the per-vertex key minimum over their vertex quadruples
+ * (vertex_min [V] u64), and the flips whose key is the minimum at all four vertices, applied to faces / face_src in place.
+ * keys [E] u64 and quads [E][6] i32 are scratch; total [1] u64 <- the number of flips. */
+int n2m_mesh_remesh_flip_round(const float* vertices, uint32_t V, int32_t* faces, const uint8_t* face_sel, int32_t* face_src, const int32_t* edges,
+                               uint32_t E, const int32_t* edge_offsets, const int32_t* edge_corners, const uint8_t* edge_feature,
+                               const uint32_t* vertex_class, const int32_t* ve_offsets, const int32_t* ve_edges, uint64_t* keys, int32_t* quads,
+                               uint64_t* vertex_min, uint64_t* total, void* stream);
+
+/* Jacobi relaxation: out[v] <- the closest point, on the one-ring triangles of v, to the mean of v's neighbours brought back into the
+ * tangent plane at v, for every vertex of class 0 (moved [V] u8 <- 1, vertex_normals [V][3] f64 <- the sum of its faces' cross products);
+ * out must be a copy of vertices on entry. */
+int n2m_mesh_remesh_relax(const float* vertices, uint32_t V, const int32_t* faces, const int32_t* edges, const uint32_t* vertex_class,
+                          const int32_t* vf_offsets, const int32_t* vf_faces, const int32_t* ve_offsets, const int32_t* ve_edges, float* out,
+                          uint8_t* moved, double* vertex_normals, void* stream);
+
+/* Puts the moved vertices of every face whose normal no longer has a positive dot product with its normal under `before`, or with the
+ * vertex normal (of n2m_mesh_remesh_relax) of one of its moved corners, back to `before` and clears their moved flag; revert [V] u8 is scratch; total [1] u64 <- the number of vertices put back. */
+int n2m_mesh_remesh_relax_revert(const float* before, float* vertices, uint32_t V, const int32_t* faces, uint32_t F, uint8_t* moved,
+                                 const double* vertex_normals, uint8_t* revert, uint64_t* total, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * mesh cleaning   (reference: pymeshlab `clean_mesh`, meshutils.py:146-188, nerf/renderer.py:537, :653 -- merge close vertices,
  * duplicate / null faces, small components, non-manifold edges and vertices; driven by nerf2mesh_amd/mesh_clean.py, rule in DESIGN.md

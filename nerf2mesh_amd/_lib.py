@@ -96,6 +96,12 @@ SIGNATURES = {
     "n2m_mesh_subdiv_midpoints": [_vp, _u32, _vp, _u32, _vp, _vp, _vp],
     "n2m_mesh_subdiv_count": [_vp, _u32, _vp, _vp, _vp],
     "n2m_mesh_subdiv_emit": [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_remesh_split_mark": [_vp, _vp, _u32, _u32, _vp, _vp, ctypes.c_double, _vp, _vp],
+    "n2m_mesh_remesh_classify": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp],
+    "n2m_mesh_remesh_collapse_cost": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp],
+    "n2m_mesh_remesh_flip_round": [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_remesh_relax": [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_remesh_relax_revert": [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp],
     "n2m_mesh_clean_cell_keys": [_vp, _u32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i32, _i32, _i32, _vp, _vp],
     "n2m_mesh_clean_merge_round": [_vp, _u32, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp],
     "n2m_mesh_clean_repoint": [_vp, _u32, _vp, _vp, _vp],

@@ -128,10 +128,11 @@ def clean_mesh(vertices, triangles, v_pct=1, min_f=8, min_d=5, repair=True, reme
     than one fan gets one new vertex, for the fan of its first (face, corner).  Unreferenced vertices are then dropped.
 
     Returns (v [V', 3] float32, f [F', 3] int32, face_src [F'] int64): surviving faces and input vertices keep their relative order,
-    the step-7 vertices follow them, face_src is each face's index in the input.  remesh=True (isotropic re-meshing) is not built.
+    the step-7 vertices follow them, face_src is each face's index in the input.  remesh=True is not wired in here and raises
+    NotImplementedError: the isotropic re-meshing itself is mesh_remesh.remesh_isotropic.
     stats: optional dict, filled with the counts of STAT_KEYS."""
     if remesh:
-        raise NotImplementedError("clean_mesh: remesh=True (isotropic explicit re-meshing) is not built on the device")
+        raise NotImplementedError("clean_mesh: remesh=True (isotropic explicit re-meshing) is not wired into clean_mesh; call mesh_remesh.remesh_isotropic")
     if not (v_pct >= 0 and min_f >= 0 and min_d >= 0):
         raise ValueError(f"clean_mesh: v_pct, min_f and min_d must be >= 0, got {v_pct}, {min_f}, {min_d}")
     vertices, faces = _check_input("clean_mesh", vertices, triangles)

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Wall time of the device mesh passes (nerf2mesh_amd/mesh_simplify.py): decimation to 3e5 faces of the marching-cubes surfaces of a
 sphere and of "lego boxes" (a steep sigmoid of the distance to the synthetic lego stand-in's boxes, synthetic.boxes -- flat faces and sharp
-edges, not the density of a trained model) at 256^3 and 512^3, and one refine_and_decimate on a ~300 k-face mesh.  Prints one JSON object.
+edges, not the density of a trained model) at 256^3 and 512^3, and one refine_and_decimate on a ~300 k-face mesh; under "remesh", the
+isotropic re-meshing (nerf2mesh_amd/mesh_remesh.py) of the two 256^3 surfaces at 1.5 x their mean edge length and one
+refine_and_decimate(remesh=True) on the same ~300 k-face mesh.  Prints one JSON object.
 
     timeout -k 10 600 python tools/mesh_bench.py"""
 import json
@@ -14,6 +16,7 @@ import torch
 
 from nerf2mesh_amd import synthetic as S
 from nerf2mesh_amd.marching_cubes import marching_cubes
+from nerf2mesh_amd.mesh_remesh import remesh_isotropic
 from nerf2mesh_amd.mesh_simplify import decimate
 
 
@@ -68,6 +71,32 @@ def main():
     out, sec = timed(lambda: model.refine_and_decimate())
     res["refine_and_decimate"] = {"faces_in": out["before"]["faces"], "faces_out": out["after"]["faces"], "seconds": round(sec, 4),
                                   "decimate_class": out["decimate"], "refine_class": out["refine"]}
+    # isotropic re-meshing: the 256^3 surfaces at 1.5 x their mean edge length, 3 iterations, one warm-up call, then one timed call
+    res["remesh"] = {"meshes": []}
+    for kind in ("sphere", "lego boxes"):
+        vol, iso = volume(kind, 256)
+        v, f = marching_cubes(vol, iso, div=255.0, mul=2.0, add=-1.0)
+        del vol
+        e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]).long()
+        target_len = 1.5 * float((v[e[:, 0]] - v[e[:, 1]]).norm(dim=1).mean())      # every edge twice on a closed surface: the same mean
+        remesh_isotropic(v, f, target_len)
+        stats = {}
+        (rv, rf, _), sec = timed(lambda: remesh_isotropic(v, f, target_len, stats=stats))
+        res["remesh"]["meshes"].append({"mesh": kind, "reso": 256, "target_len": round(target_len, 6), "faces_in": int(f.shape[0]),
+                                        "faces_out": int(rf.shape[0]), "seconds": round(sec, 4),
+                                        "rounds": [{k: it[k] for k in ("split_rounds", "collapse_rounds", "flip_rounds", "relax_reverts", "faces")}
+                                                   for it in stats["iterations"]]})
+        print(json.dumps(res["remesh"]["meshes"][-1]), file=sys.stderr, flush=True)
+    torch.manual_seed(0)
+    v, f = S.scene_mesh(300_000)
+    model = NeRFNetwork(make_options(O=True, bound=1, dt_gamma=0, stage=1)).cuda()
+    model.init_stage1(v, f)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    model.triangles_errors.copy_(torch.rand(f.shape[0], device="cuda", generator=g))
+    model.triangles_errors_cnt.fill_(1)
+    out, sec = timed(lambda: model.refine_and_decimate(remesh=True))
+    res["remesh"]["refine_and_decimate"] = {"faces_in": out["before"]["faces"], "faces_out": out["after"]["faces"], "seconds": round(sec, 4),
+                                            "decimate_class": out["decimate"], "refine_class": out["refine"], "remesh": out["remesh"]}
     print(json.dumps(res))
 
 
