@@ -589,6 +589,34 @@ int n2m_mesh_remesh_relax(const float* vertices, uint32_t V, const int32_t* face
 int n2m_mesh_remesh_relax_revert(const float* before, float* vertices, uint32_t V, const int32_t* faces, uint32_t F, uint8_t* moved,
                                  const double* vertex_normals, uint8_t* revert, uint64_t* total, void* stream);
 
+/* ---- closest-point queries (csrc/meshquery.hip): a linear bounding-volume hierarchy (Karras 2012) over the faces with three
+ * distinct vertex indices, n of them, and its traversal; driven by nerf2mesh_amd/mesh_query.py.  Node ids: internal nodes 0 .. n - 2 (0 the
+ * root), leaf j is node n - 1 + j (with n == 1 the only node, 0, is the leaf).  leaf_face [n] i32 = the face of leaf j, in key order;
+ * children [n - 1][2] i32; parent [2n - 1] i32, -1 at the root; boxes [2n - 1][6] f32 = min xyz, max xyz of the vertex coordinates below
+ * the node (exact, whatever order the children arrived in). */
+
+/* keys [F] i64 <- (30-bit Morton code of the face's centroid) << 32 | f, the centroid (fp64) in cell min(1023, floor((x - lo) * scale))
+ * per axis (0 for a NaN); INT64_MAX for a face with a repeated vertex index, which sorts behind every indexed face */
+int n2m_mesh_bvh_morton(const float* vertices, const int32_t* faces, uint32_t F, double lo_x, double lo_y, double lo_z, double scale_x,
+                        double scale_y, double scale_z, int64_t* keys, void* stream);
+
+/* children, parent <- the radix tree of n ascending, pairwise different keys: one thread per internal node */
+int n2m_mesh_bvh_hierarchy(const uint64_t* keys, uint32_t n, int32_t* children, int32_t* parent, void* stream);
+
+/* boxes <- bottom up, one thread per leaf; counters [n - 1] i32 are scratch (zeroed by the call): the second thread to arrive at an
+ * internal node forms its box */
+int n2m_mesh_bvh_refit(const float* vertices, const int32_t* faces, const int32_t* leaf_face, uint32_t n, const int32_t* children,
+                       const int32_t* parent, float* boxes, int32_t* counters, void* stream);
+
+/* For every point [N][3] f64: the lexicographic minimum of (d2, face id) over the indexed faces, d2 = |c - p|^2 (f64) with c the closest
+ * point of the face by the Voronoi-region walk of csrc/n2m_mesh.hpp; d2 [N] f64, face [N] i32, point [N][3] f64 <- d2, the face, its c.
+ * A face whose d2 is not finite never wins; no face at all: d2 = inf, face = -1, point = NaN.  prune = 1 skips a subtree whose box is
+ * further from the point than d2 + slack_abs + slack_rel * d2 (strictly); prune = 0 visits every leaf.  A hierarchy deeper than 64 levels
+ * (none that n2m_mesh_bvh_hierarchy builds) is reported as face = -2, d2 = NaN. */
+int n2m_mesh_closest(const float* vertices, const int32_t* faces, const int32_t* leaf_face, uint32_t n, const int32_t* children, const float* boxes,
+                     const double* points, uint32_t N, int prune, double slack_abs, double slack_rel, double* d2, int32_t* face, double* point,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * mesh cleaning   (reference: pymeshlab `clean_mesh`, meshutils.py:146-188, nerf/renderer.py:537, :653 -- merge close vertices,
  * duplicate / null faces, small components, non-manifold edges and vertices; driven by nerf2mesh_amd/mesh_clean.py, rule in DESIGN.md

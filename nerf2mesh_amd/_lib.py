@@ -102,6 +102,10 @@ SIGNATURES = {
     "n2m_mesh_remesh_flip_round": [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_mesh_remesh_relax": [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_mesh_remesh_relax_revert": [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_bvh_morton": [_vp, _vp, _u32] + [ctypes.c_double] * 6 + [_vp, _vp],
+    "n2m_mesh_bvh_hierarchy": [_vp, _u32, _vp, _vp, _vp],
+    "n2m_mesh_bvh_refit": [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp],
+    "n2m_mesh_closest": [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _int, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp],
     "n2m_mesh_clean_cell_keys": [_vp, _u32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _i32, _i32, _i32, _vp, _vp],
     "n2m_mesh_clean_merge_round": [_vp, _u32, _vp, _vp, _vp, _i32, _i32, _i32, ctypes.c_double, _vp, _vp, _vp, _vp, _vp],
     "n2m_mesh_clean_repoint": [_vp, _u32, _vp, _vp, _vp],

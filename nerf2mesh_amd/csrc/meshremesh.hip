@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "n2m_common.hpp"
+#include "n2m_mesh.hpp"
 
 namespace {
 
@@ -20,19 +21,13 @@ constexpr uint32_t kFrozen = 1u, kBoundary = 2u, kFeature = 4u;     // vertex cl
 constexpr uint64_t kNoKey = ~0ull;
 constexpr int64_t kMaxGain = 1ll << 30;
 
-struct D3 { double x, y, z; };
-
 __device__ __forceinline__ D3 ld3(const float* __restrict__ v, int32_t i) {
     return D3{(double)v[3 * (int64_t)i], (double)v[3 * (int64_t)i + 1], (double)v[3 * (int64_t)i + 2]};
 }
 __device__ __forceinline__ void st3(float* __restrict__ v, int32_t i, D3 p) {
     v[3 * (int64_t)i] = (float)p.x; v[3 * (int64_t)i + 1] = (float)p.y; v[3 * (int64_t)i + 2] = (float)p.z;
 }
-__device__ __forceinline__ D3 add(D3 a, D3 b) { return D3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ D3 sub(D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 mul(D3 a, double s) { return D3{a.x * s, a.y * s, a.z * s}; }
 __device__ __forceinline__ D3 cross(D3 a, D3 b) { return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 __device__ __forceinline__ D3 round_f32(D3 p) { return D3{(double)(float)p.x, (double)(float)p.y, (double)(float)p.z}; }
 __device__ __forceinline__ D3 face_normal(const float* __restrict__ verts, const int32_t* __restrict__ t) {
     const D3 p0 = ld3(verts, t[0]);
@@ -251,27 +246,7 @@ __global__ void rm_flip_apply_kernel(uint32_t E, const uint64_t* __restrict__ ke
 }
 
 // ------------------------------------------------------------------------------------------------------------ relax
-// closest point of the triangle (a, b, c) to p: the Voronoi-region walk (vertex a, vertex b, edge ab, vertex c, edge ac, edge bc, inside)
-__device__ __forceinline__ D3 closest_on_triangle(D3 p, D3 a, D3 b, D3 c) {
-    const D3 ab = sub(b, a), ac = sub(c, a), ap = sub(p, a);
-    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
-    if (d1 <= 0.0 && d2 <= 0.0) return a;
-    const D3 bp = sub(p, b);
-    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
-    if (d3 >= 0.0 && d4 <= d3) return b;
-    const double vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) return add(a, mul(ab, d1 / (d1 - d3)));
-    const D3 cp = sub(p, c);
-    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
-    if (d6 >= 0.0 && d5 <= d6) return c;
-    const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) return add(a, mul(ac, d2 / (d2 - d6)));
-    const double va = d3 * d6 - d5 * d4;
-    if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) return add(b, mul(sub(c, b), (d4 - d3) / ((d4 - d3) + (d5 - d6))));
-    const double s = (va + vb) + vc;
-    return add(add(a, mul(ab, vb / s)), mul(ac, vc / s));
-}
-
+// (closest_on_triangle, the Voronoi-region walk, is in n2m_mesh.hpp: csrc/meshquery.hip shares it)
 __global__ void rm_relax_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ edges,
                                 const uint32_t* __restrict__ vclass, const int32_t* __restrict__ vf_off, const int32_t* __restrict__ vf_idx,
                                 const int32_t* __restrict__ ve_off, const int32_t* __restrict__ ve_idx, uint32_t V, float* __restrict__ out,

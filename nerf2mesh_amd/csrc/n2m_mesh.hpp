@@ -1,5 +1,6 @@
-// Device helpers shared by the mesh passes (meshclean.hip, uvatlas.hip): exact fp64 face frames, the lock-free union-find whose roots
-// are their trees' minima, and the order-preserving integer encoding of floats for atomic min / max.
+// Device helpers shared by the mesh passes (meshclean.hip, uvatlas.hip, meshremesh.hip, meshquery.hip): exact fp64 face frames, the
+// lock-free union-find whose roots are their trees' minima, the order-preserving integer encoding of floats for atomic min / max, and
+// the fp64 closest point of a triangle.
 #pragma once
 #include "n2m_common.hpp"
 
@@ -53,5 +54,33 @@ __device__ __forceinline__ uint32_t fenc(float x) {
     return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
 }
 __device__ __forceinline__ float fdec(uint32_t e) { return __uint_as_float(e ^ (~(uint32_t)((int32_t)e >> 31) | 0x80000000u)); }
+
+// fp64 points: every value a mesh pass decides on is fp64 + - * / (IEEE correctly rounded, -ffp-contract=off)
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 add(D3 a, D3 b) { return D3{a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ D3 sub(D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ D3 mul(D3 a, double s) { return D3{a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+
+// closest point of the triangle (a, b, c) to p: the Voronoi-region walk (vertex a, vertex b, edge ab, vertex c, edge ac, edge bc, inside)
+__device__ __forceinline__ D3 closest_on_triangle(D3 p, D3 a, D3 b, D3 c) {
+    const D3 ab = sub(b, a), ac = sub(c, a), ap = sub(p, a);
+    const double d1 = dot(ab, ap), d2 = dot(ac, ap);
+    if (d1 <= 0.0 && d2 <= 0.0) return a;
+    const D3 bp = sub(p, b);
+    const double d3 = dot(ab, bp), d4 = dot(ac, bp);
+    if (d3 >= 0.0 && d4 <= d3) return b;
+    const double vc = d1 * d4 - d3 * d2;
+    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) return add(a, mul(ab, d1 / (d1 - d3)));
+    const D3 cp = sub(p, c);
+    const double d5 = dot(ab, cp), d6 = dot(ac, cp);
+    if (d6 >= 0.0 && d5 <= d6) return c;
+    const double vb = d5 * d2 - d1 * d6;
+    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) return add(a, mul(ac, d2 / (d2 - d6)));
+    const double va = d3 * d6 - d5 * d4;
+    if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) return add(b, mul(sub(c, b), (d4 - d3) / ((d4 - d3) + (d5 - d6))));
+    const double s = (va + vb) + vc;
+    return add(add(a, mul(ab, vb / s)), mul(ac, vc / s));
+}
 
 }  // namespace

@@ -13,6 +13,7 @@ import math
 import torch
 
 from . import _lib as L
+from .mesh_query import MeshIndex
 from .mesh_simplify import _check_mask, _check_mesh, _compact, _edges, _offsets, _topology
 
 _p = L.ptr
@@ -140,7 +141,7 @@ def _flip_pass(v, f, sel, src, cos_f, devs):
     return rounds
 
 
-def _relax_pass(v, f, sel, cos_f):
+def _relax_pass(v, f, sel, cos_f, index=None):
     dev = v.device
     s = L.stream()
     V, F = int(v.shape[0]), int(f.shape[0])
@@ -150,6 +151,13 @@ def _relax_pass(v, f, sel, cos_f):
     vnormal = torch.empty(V, 3, dtype=torch.float64, device=dev)      # written (and later read) for the moved vertices only
     L.call("n2m_mesh_remesh_relax", _p(v), V, _p(f), _p(t.edges), _p(t.vclass), _p(t.vf_off), _p(t.vf_faces), _p(t.ve_off), _p(t.ve_edges), _p(out),
            _p(moved), _p(vnormal), s)
+    projected = 0
+    if index is not None:                                        # every moved vertex onto the input surface, rounded to fp32 once
+        ids = torch.nonzero(moved).reshape(-1)                   # host read: the number of moved vertices
+        projected = int(ids.shape[0])
+        if projected:
+            _, face, hit = index.closest(out[ids])
+            out[ids] = torch.where((face >= 0)[:, None], hit.float(), out[ids])
     revert = torch.empty(V, dtype=torch.uint8, device=dev)
     total = torch.empty(1, dtype=torch.int64, device=dev)
     reverted = 0
@@ -157,11 +165,11 @@ def _relax_pass(v, f, sel, cos_f):
         L.call("n2m_mesh_remesh_relax_revert", _p(v), _p(out), V, _p(f), F, _p(moved), _p(vnormal), _p(revert), _p(total), s)
         n = int(total)                                           # the pass's host read
         if n == 0:
-            return out, reverted
+            return out, reverted, projected
         reverted += n
 
 
-def remesh_isotropic(vertices, triangles, target_len, iterations=3, selected=None, feature_deg=30.0, stats=None):
+def remesh_isotropic(vertices, triangles, target_len, iterations=3, selected=None, feature_deg=30.0, stats=None, project=False):
     """Isotropic explicit re-meshing towards the edge length `target_len` (absolute; the reference's `PureValue`).
 
     vertices float32 [V, 3], triangles int32/int64 [F, 3], CUDA.  Returns (v [V', 3] float32, f [F', 3] int32, face_src [F'] int64).
@@ -182,8 +190,14 @@ def remesh_isotropic(vertices, triangles, target_len, iterations=3, selected=Non
 
     Edges with more than two faces freeze their endpoints: non-manifold input is kept, not repaired.
 
+    project: after every relaxation, replace every vertex it moved by the closest point of the *input* surface (all of its faces, through
+    a mesh_query.MeshIndex built once per call) to its relaxed position, rounded to fp32 once; the undoing of moves that would flip a face
+    runs after that, against the positions before the pass.  Without it the surface drifts inward a little with every iteration (DESIGN
+    4.15).  Feature and frozen vertices never move, so they are never projected.  False leaves every output bit as it was.
+
     stats: optional dict, filled with {"iterations": [{"split_rounds", "collapse_rounds", "flip_rounds", "relax_reverts", "faces",
-    "valence_dev": [before the first flip round, after every round]}, ...]}."""
+    "valence_dev": [before the first flip round, after every round]}, ...]}; with project=True every entry also has "projected", the
+    number of vertices the pass projected."""
     vertices, faces = _check_mesh("remesh_isotropic", vertices, triangles)
     dev = vertices.device
     F = int(faces.shape[0])
@@ -208,6 +222,7 @@ def remesh_isotropic(vertices, triangles, target_len, iterations=3, selected=Non
         s = L.stream()
         v, f = vertices.clone(), faces.clone()
         src = torch.arange(F, dtype=torch.int32, device=dev)
+        index = MeshIndex(vertices, faces) if project else None
         for _ in range(iterations):
             if int(f.shape[0]) == 0:
                 break
@@ -215,10 +230,12 @@ def remesh_isotropic(vertices, triangles, target_len, iterations=3, selected=Non
             f, sel, src, n_collapse = _collapse_pass(v, f, sel, src, lo2, hi2, cos_f)
             devs = [] if stats is not None else None
             n_flip = _flip_pass(v, f, sel, src, cos_f, devs)
-            v, n_revert = _relax_pass(v, f, sel, cos_f)
+            v, n_revert, n_project = _relax_pass(v, f, sel, cos_f, index)
             if stats is not None:
                 stats["iterations"].append({"split_rounds": n_split, "collapse_rounds": n_collapse, "flip_rounds": n_flip, "relax_reverts": n_revert,
                                             "faces": int(f.shape[0]), "valence_dev": [int(x) for x in torch.stack(devs).tolist()]})
+                if project:
+                    stats["iterations"][-1]["projected"] = n_project
         # drop the vertices the collapses left unreferenced, stably
         V = int(v.shape[0])
         ref = torch.empty(V, dtype=torch.uint8, device=dev)

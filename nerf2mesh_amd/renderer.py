@@ -581,7 +581,7 @@ class NeRFRenderer(nn.Module):
 
     # ------------------------------------------------------------------------------------------ stage 1
     @torch.no_grad()
-    def refine_and_decimate(self, save_path=None, remesh=False):
+    def refine_and_decimate(self, save_path=None, remesh=False, remesh_project=False):
         """Stage-1 mesh refinement (nerf/renderer.py:209-294, meshutils.py:191-231) on the device.  The accumulated per-face errors,
         averaged by their counts, classify the seen faces of the inner mesh: above the 90th percentile -> 2 (subdivide), below the 50th
         -> 1 (decimate), numpy.percentile's linear rule; SDF: every face is 1.  Cascade 0 is decimated on the class-1 faces
@@ -594,7 +594,9 @@ class NeRFRenderer(nn.Module):
         re-meshed isotropically towards that edge length between the decimation and the subdivision
         (mesh_remesh.remesh_isotropic, 3 iterations, selected-only: meshutils.py:208-209), the classes carried through its face sources,
         and the result reports "remesh": {"faces_before", "faces_after"}.  It is the project's own rule for the published algorithm
-        (DESIGN 4.14), not MeshLab's vertex positions.
+        (DESIGN 4.14), not MeshLab's vertex positions.  remesh_project=True passes project=True on: every relaxed vertex is brought back
+        onto the mesh the re-meshing started from (MeshLab's `reprojectflag`), and "remesh" also reports "projected", the
+        vertices projected per iteration.
         Differences: the non-manifold repairs after the re-meshing (:212-213; the device passes keep a manifold input manifold) are not
         done, and without `remesh` neither is the re-meshing."""
         from .mesh_simplify import decimate, subdivide_midpoint
@@ -633,7 +635,12 @@ class NeRFRenderer(nn.Module):
                 if remesh and opt.refine_remesh_size > 0 and n_dec_after:
                     from .mesh_remesh import remesh_isotropic
                     remeshed = {"faces_before": int(f.shape[0])}
-                    v, f, src = remesh_isotropic(v, f, opt.refine_remesh_size, iterations=3, selected=mask == 1)
+                    if remesh_project:
+                        rstats = {}
+                        v, f, src = remesh_isotropic(v, f, opt.refine_remesh_size, iterations=3, selected=mask == 1, stats=rstats, project=True)
+                        remeshed["projected"] = [it["projected"] for it in rstats["iterations"]]
+                    else:
+                        v, f, src = remesh_isotropic(v, f, opt.refine_remesh_size, iterations=3, selected=mask == 1)
                     mask = mask[src]
                     remeshed["faces_after"] = int(f.shape[0])
                 if opt.refine_size > 0 and n_ref:

@@ -549,15 +549,18 @@ class Stage1Trainer:
         self.global_step, self.covered_seen, self.view_cache, self._dirs, self.gen = keep
 
     @torch.no_grad()
-    def refine_mesh(self, src=0, remesh=False):
+    def refine_mesh(self, src=0, remesh=False, remesh_project=False):
         """The reference's stage-1 refinement step (nerf/utils.py:1204-1211): the error accumulators are summed over the ranks, rank `src`
         refines and decimates the mesh (NeRFRenderer.refine_and_decimate), then every rank re-initialises stage 1 on the new mesh -- fresh
         offsets, optimizer, schedule and Laplacian; the step count, the view cache and the background generator stay (_reattach).
         Collective when world > 1.  A Stage1Engine
         built before this call refuses to step (its mesh is gone): build a new one.  `remesh` is passed on to refine_and_decimate (the
-        isotropic re-meshing of the decimated faces, off by default).  Returns refine_and_decimate's counts on rank `src`, None elsewhere."""
+        isotropic re-meshing of the decimated faces, off by default), and so is `remesh_project` (its re-projection onto the mesh it started from).  Returns refine_and_decimate's counts on rank `src`, None elsewhere."""
         self.sync_refine_state()
-        stats = (self.model.refine_and_decimate(remesh=True) if remesh else self.model.refine_and_decimate()) if self.rank == src else None
+        if remesh and remesh_project:
+            stats = self.model.refine_and_decimate(remesh=True, remesh_project=True) if self.rank == src else None
+        else:
+            stats = (self.model.refine_and_decimate(remesh=True) if remesh else self.model.refine_and_decimate()) if self.rank == src else None
         if self.world > 1:
             self.broadcast_mesh(src)
         else:

@@ -3,7 +3,10 @@
 sphere and of "lego boxes" (a steep sigmoid of the distance to the synthetic lego stand-in's boxes, synthetic.boxes -- flat faces and sharp
 edges, not the density of a trained model) at 256^3 and 512^3, and one refine_and_decimate on a ~300 k-face mesh; under "remesh", the
 isotropic re-meshing (nerf2mesh_amd/mesh_remesh.py) of the two 256^3 surfaces at 1.5 x their mean edge length and one
-refine_and_decimate(remesh=True) on the same ~300 k-face mesh.  Prints one JSON object.
+refine_and_decimate(remesh=True) on the same ~300 k-face mesh, with and without the re-projection (project=True); under "query", the
+closest-point index (nerf2mesh_amd/mesh_query.py) of the 256^3 sphere: build, 1 M surface-sample queries, and 2^16 queries through the
+exhaustive device scan (prune = 0).  Every decimated and re-meshed output reports its sampled one-sided distances to and from its input
+(mesh_distance, 1e5 samples a side).  Prints one JSON object.
 
     timeout -k 10 600 python tools/mesh_bench.py"""
 import json
@@ -16,6 +19,7 @@ import torch
 
 from nerf2mesh_amd import synthetic as S
 from nerf2mesh_amd.marching_cubes import marching_cubes
+from nerf2mesh_amd.mesh_query import MeshIndex, mesh_distance, sample_surface
 from nerf2mesh_amd.mesh_remesh import remesh_isotropic
 from nerf2mesh_amd.mesh_simplify import decimate
 
@@ -26,6 +30,34 @@ def timed(fn):
     out = fn()
     torch.cuda.synchronize()
     return out, time.perf_counter() - t
+
+
+def distances(v_out, f_out, v_in, f_in, n=100_000):
+    """Sampled one-sided distances between an output mesh and its input: mean and maximum, each way."""
+    d = mesh_distance(v_out, f_out, v_in, f_in, n=n, generator=torch.Generator(device="cuda").manual_seed(0))
+    return {"out_to_in": {"mean": d["mean_ab"], "max": d["max_ab"]}, "in_to_out": {"mean": d["mean_ba"], "max": d["max_ba"]}, "samples": n}
+
+
+def query_bench():
+    """The 256^3 marching-cubes sphere: index build, 1 M pruned queries, 2^16 queries that visit every leaf; one warm-up call each."""
+    vol, iso = volume("sphere", 256)
+    v, f = marching_cubes(vol, iso, div=255.0, mul=2.0, add=-1.0)
+    del vol
+    g = torch.Generator(device="cuda").manual_seed(0)
+    pts, _ = sample_surface(v, f, 1_000_000, g)
+    MeshIndex(v, f)
+    index, t_build = timed(lambda: MeshIndex(v, f))
+    index.closest(pts[:4096])
+    (d2, _, _), t_pruned = timed(lambda: index.closest(pts))
+    few = pts[:1 << 16]
+    index.closest(few[:256], prune=False)
+    (e2, _, _), t_scan = timed(lambda: index.closest(few, prune=False))
+    assert torch.equal(d2[:1 << 16].view(torch.int64), e2.view(torch.int64))
+    per_pruned, per_scan = t_pruned / pts.shape[0], t_scan / few.shape[0]
+    return {"mesh": "sphere", "reso": 256, "faces": int(f.shape[0]), "build_seconds": round(t_build, 5),
+            "pruned": {"queries": int(pts.shape[0]), "seconds": round(t_pruned, 5), "ns_per_query": round(per_pruned * 1e9, 2)},
+            "prune0": {"queries": int(few.shape[0]), "seconds": round(t_scan, 5), "ns_per_query": round(per_scan * 1e9, 2)},
+            "prune0_over_pruned_per_query": round(per_scan / per_pruned, 1)}
 
 
 def volume(kind, R):
@@ -56,7 +88,7 @@ def main():
             stats = {}
             (dv, df, _), sec = timed(lambda: decimate(v, f, target, stats=stats))
             res["decimate"].append({"mesh": kind, "reso": R, "faces_in": int(f.shape[0]), "faces_out": int(df.shape[0]), "seconds": round(sec, 4),
-                                    "rounds": stats["rounds"], "faces_per_round": stats["faces"]})
+                                    "rounds": stats["rounds"], "faces_per_round": stats["faces"], "distance": distances(dv, df, v, f)})
             print(json.dumps(res["decimate"][-1]), file=sys.stderr, flush=True)
     # one refine_and_decimate on a ~300 k-face mesh with a random error field
     from nerf2mesh_amd.network import NeRFNetwork
@@ -85,7 +117,16 @@ def main():
         res["remesh"]["meshes"].append({"mesh": kind, "reso": 256, "target_len": round(target_len, 6), "faces_in": int(f.shape[0]),
                                         "faces_out": int(rf.shape[0]), "seconds": round(sec, 4),
                                         "rounds": [{k: it[k] for k in ("split_rounds", "collapse_rounds", "flip_rounds", "relax_reverts", "faces")}
-                                                   for it in stats["iterations"]]})
+                                                   for it in stats["iterations"]], "distance": distances(rv, rf, v, f)})
+        print(json.dumps(res["remesh"]["meshes"][-1]), file=sys.stderr, flush=True)
+        remesh_isotropic(v, f, target_len, project=True)
+        stats = {}
+        (rv, rf, _), sec = timed(lambda: remesh_isotropic(v, f, target_len, stats=stats, project=True))
+        res["remesh"]["meshes"].append({"mesh": kind, "reso": 256, "project": True, "target_len": round(target_len, 6), "faces_in": int(f.shape[0]),
+                                        "faces_out": int(rf.shape[0]), "seconds": round(sec, 4),
+                                        "rounds": [{k: it[k] for k in ("split_rounds", "collapse_rounds", "flip_rounds", "relax_reverts", "faces",
+                                                                       "projected")} for it in stats["iterations"]],
+                                        "distance": distances(rv, rf, v, f)})
         print(json.dumps(res["remesh"]["meshes"][-1]), file=sys.stderr, flush=True)
     torch.manual_seed(0)
     v, f = S.scene_mesh(300_000)
@@ -97,6 +138,8 @@ def main():
     out, sec = timed(lambda: model.refine_and_decimate(remesh=True))
     res["remesh"]["refine_and_decimate"] = {"faces_in": out["before"]["faces"], "faces_out": out["after"]["faces"], "seconds": round(sec, 4),
                                             "decimate_class": out["decimate"], "refine_class": out["refine"], "remesh": out["remesh"]}
+    res["query"] = query_bench()
+    print(json.dumps(res["query"]), file=sys.stderr, flush=True)
     print(json.dumps(res))
 
 
