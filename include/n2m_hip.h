@@ -730,6 +730,29 @@ int n2m_uv_face_metrics(const float* vt, const int32_t* ft, const double* double
  * (row, column); ties: smallest row, then column); destinations with no source in range are left as they are. */
 int n2m_texture_pad_nearest(uint8_t* feats, const uint8_t* role, uint32_t H, uint32_t W, uint32_t C, uint32_t radius, void* stream);
 
+/* The exported asset's fragment shader (reference: renderer.html:424-472 -- diffuse texel + sigmoid(2-layer MLP(view dir, specular texel)),
+ * clamped), one thread per pixel of a rasterised view.  The cascades' meshes are concatenated the way `self.triangles` is; cascade c owns
+ * the faces [face_begin[c], face_begin[c + 1]) (the last one up to F) and has its own pair of u8 [Ht][Wt][3] textures. */
+#define N2M_ASSET_MAX 8
+typedef struct {
+    const uint8_t* feat0[N2M_ASSET_MAX]; const uint8_t* feat1[N2M_ASSET_MAX];      /* diffuse / specular-feature texture per cascade */
+    uint32_t Ht[N2M_ASSET_MAX]; uint32_t Wt[N2M_ASSET_MAX];
+    uint32_t face_begin[N2M_ASSET_MAX];                                             /* ascending, face_begin[0] = 0 */
+    uint32_t count;
+} N2mAssetTable;   /* HOST struct, handed to the kernel by value */
+enum { N2M_ASSET_FULL = 0, N2M_ASSET_DIFFUSE = 1, N2M_ASSET_SPECULAR = 2 };
+enum { N2M_ASSET_NEAREST = 0, N2M_ASSET_LINEAR = 1 };
+/* rast [H][W][4] as n2m_rasterize_forward writes it (barycentrics of the face's first two vertices, z/w, face id + 1; 0 = empty),
+ * ft [F][3] i32 into vt [T][2] f32, rays_d [H W][3] f32 un-normalised, w0 [32][6] / w1 [3][32] f32 (specular_net's layout, no bias;
+ * input order: direction, then the specular texel) -> rgb [H W][3] f32.  Per covered pixel: uv = sum_k bary_k vt[ft[face][k]];
+ * nearest: texel (row clamp(floor(v Ht)), column clamp(floor(u Wt))) -- row index grows with v, texel centre ((x + .5) / Wt, (y + .5) / Ht),
+ * the bake's convention; linear: the four texels around (u Wt - .5, v Ht - .5), indices clamped at the border, fp32 weights; texel / 255;
+ * d = rays_d rsqrt(max(|rays_d|^2, 1e-20)); spec = sigmoid(w1 relu(w0 [d, feat1]));  full: clamp(feat0 + spec, 0, 1), diffuse: feat0,
+ * specular: spec.  Empty pixels, and pixels whose face id or uv indices are out of range, are written 0. */
+int n2m_asset_shade(const float* rast, const int32_t* ft, const float* vt, const float* rays_d, const N2mAssetTable* table,
+                    const float* w0, const float* w1, uint32_t F, uint32_t T, uint32_t H, uint32_t W, int mode, int filter,
+                    float* rgb, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------
  * freqencoder   (reference: freqencoder/src/freqencoder.h:6-10, freqencoder/src/bindings.cpp:5-8)
  * ---------------------------------------------------------------------------------------------------- */

@@ -128,6 +128,7 @@ SIGNATURES = {
     "n2m_uv_canvas_evict": [_vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp],
     "n2m_uv_face_metrics": [_vp, _vp, _vp, _u32, _i32, _i32, _vp, _vp, _vp],
     "n2m_texture_pad_nearest": [_vp, _vp, _u32, _u32, _u32, _u32, _vp],
+    "n2m_asset_shade": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _int, _int, _vp, _vp],
     "n2m_freq_encode_forward": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_get_rays": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
@@ -222,6 +223,15 @@ EMA_MAX = 16
 class EmaDesc(ctypes.Structure):
     """N2mEmaDesc of include/n2m_hip.h."""
     _fields_ = [("shadow", _vp * EMA_MAX), ("param", _vp * EMA_MAX), ("numel", _u32 * EMA_MAX), ("count", _u32)]
+
+
+ASSET_MAX = 8
+
+
+class AssetTable(ctypes.Structure):
+    """N2mAssetTable of include/n2m_hip.h."""
+    _fields_ = [("feat0", _vp * ASSET_MAX), ("feat1", _vp * ASSET_MAX), ("Ht", _u32 * ASSET_MAX), ("Wt", _u32 * ASSET_MAX),
+                ("face_begin", _u32 * ASSET_MAX), ("count", _u32)]
 
 
 PEER_MAX = 8

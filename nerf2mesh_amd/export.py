@@ -124,6 +124,44 @@ def write_mlp_json(path, model):
     return mlp
 
 
+def read_obj(path):
+    """(v [V,3] float32, f [F,3] int32, vt [T,2] float32, ft [F,3] int32) of an OBJ as `write_obj` lays it out: `v`, `vt`, `f a/ta b/tb c/tc`
+    with 1-based indices; `mtllib` / `usemtl` are ignored.  The v flip is undone (vt[:, 1] = 1 - the file's value, in float32 like the
+    flip on the way out), so vt is back in the space of the atlas handed to `bake_textures`."""
+    v, vt, f, ft = [], [], [], []
+    with open(path) as fp:
+        for line in fp:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == "v":
+                v.append((t[1], t[2], t[3]))
+            elif t[0] == "vt":
+                vt.append((t[1], t[2]))
+            elif t[0] == "f":
+                if len(t) != 4:
+                    raise ValueError(f"{path}: only triangles are supported, got {line.strip()!r}")
+                corners = [c.split("/") for c in t[1:]]
+                if any(len(c) < 2 or not c[1] for c in corners):
+                    raise ValueError(f"{path}: face without texture indices (expected `f a/ta b/tb c/tc`), got {line.strip()!r}")
+                f.append([int(c[0]) - 1 for c in corners])
+                ft.append([int(c[1]) - 1 for c in corners])
+    v = np.asarray(v, dtype=np.float32).reshape(-1, 3)
+    vt = np.asarray(vt, dtype=np.float32).reshape(-1, 2)
+    vt[:, 1] = np.float32(1) - vt[:, 1]
+    return v, np.asarray(f, dtype=np.int32).reshape(-1, 3), vt, np.asarray(ft, dtype=np.int32).reshape(-1, 3)
+
+
+def read_mlp_json(path):
+    """`mlp.json` back in specular_net's own layout: {"w0" [32,6] float32 (net.0.weight), "w1" [3,32] float32 (net.1.weight), "bound",
+    "cascade"} -- the file holds the transposes (`write_mlp_json`)."""
+    with open(path) as fp:
+        mlp = json.load(fp)
+    return {"w0": np.ascontiguousarray(np.asarray(mlp["net.0.weight"], dtype=np.float32).T),
+            "w1": np.ascontiguousarray(np.asarray(mlp["net.1.weight"], dtype=np.float32).T),
+            "bound": mlp["bound"], "cascade": mlp["cascade"]}
+
+
 # ------------------------------------------------------------------------------------------------ mesh filters
 # The two pymeshlab selections export_stage0 uses between marching cubes and the PLY (meshutils.py:63-143), on device tensors.
 # (clean_mesh and decimate_mesh, meshutils.py:27-60,146-190, run on the device too: mesh_clean.clean_mesh, mesh_simplify.decimate.)
@@ -182,3 +220,10 @@ def write_jpg(path, rgb):
     RGB -> BGR swap for cv2's channel order: the file holds the RGB image either way."""
     from PIL import Image
     Image.fromarray(np.ascontiguousarray(rgb, dtype=np.uint8), "RGB").save(path, quality=95)
+
+
+def read_jpg(path):
+    """JPEG -> [H, W, 3] uint8 RGB, row 0 first (PIL's decoder; a viewer's may differ in the last bit of a few texels)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.array(im.convert("RGB"), dtype=np.uint8)
