@@ -5,6 +5,7 @@ PyTorch fallback anywhere in the package.
 """
 import ctypes
 import os
+import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("N2M_HIP_LIB") or os.path.join(_HERE, "lib", "libn2m_hip.so")   # override: A/B builds of the same ABI
@@ -299,18 +300,20 @@ def call(name, *args):
         raise RuntimeError(f"{name} failed ({rc}): {L.n2m_last_error().decode()}")
 
 
-_BWD_CFG = [None]
+_BWD_CFG = threading.local()
 
 
 def grid_backward_config(tv_stride=1, overflow_div=1.0):
-    """n2m_grid_backward_config is PROCESS-wide state of the binned backward (row stride of the TV table, fp16 overflow margin).  Every
-    Python caller of a binned backward / binned TV entry point states what it needs right before its call -- a sharded engine (stride 2,
-    margin W) and a plain trainer or single-GPU engine (1, 1) can then live in one process without inheriting each other's setting.  The
-    last value is cached: the common case costs one tuple compare."""
+    """n2m_grid_backward_config is PER-THREAD state of the binned backward (row stride of the TV table, fp16 overflow margin; thread_local in
+    csrc/gridencoder.hip).  Every Python caller of a binned backward / binned TV entry point states what it needs right before its call --
+    a sharded engine (stride 2, margin W) and a plain trainer or single-GPU engine (1, 1) can then live in one process without inheriting
+    each other's setting.  The last value is cached PER THREAD, like the state it mirrors: the common case costs one tuple compare.  (One
+    cache for the process let the autograd worker thread's (1, 1) stand for the main thread's too, whose library state an engine had left
+    at stride 2: the next TV pass on the main thread then walked a [rows, 1] table with stride 2, past its end.)"""
     want = (int(tv_stride), float(overflow_div))
-    if _BWD_CFG[0] != want:
+    if getattr(_BWD_CFG, "value", None) != want:
         call("n2m_grid_backward_config", want[0], want[1])
-        _BWD_CFG[0] = want
+        _BWD_CFG.value = want
 
 
 _WORKSPACE = {}

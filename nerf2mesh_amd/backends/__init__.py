@@ -22,6 +22,7 @@ def install(fused_mlp=False):
     its unchanged NeRFNetwork (an import hook; call `fuse_field(nerf.network.NeRFNetwork)` yourself if the module is already loaded)."""
     if fused_mlp:
         _fuse_on_import()
+        track_torch_ema()
     p = path()
     if p not in sys.path:
         sys.path.insert(0, p)
@@ -43,9 +44,16 @@ def fuse_field(cls):
     include/n2m_mlp.h) BEHIND the unchanged class: `cls.forward` and `cls.density` are wrapped so that a call the fused kernels cover --
     device tensors, no individual codes (`c is None`), no tcnn, the two standard encoders, bias-free MLPs of the reference's shapes -- runs
     `nerf2mesh_amd.fused.fused_field / fused_density` (an autograd Function: gradients of both tables and the seven weight matrices arrive
-    as `.grad` like any other, so torch.optim.Adam / GradScaler / EMA / checkpoints work unchanged), and every other call falls through to
+    as `.grad` like any other, so torch.optim.Adam / GradScaler / checkpoints work unchanged), and every other call falls through to
     the reference's own method.  Same parameters, same state_dict, same numerics class as the reference's autocast graph (fp16 operands,
-    fp32 accumulation: tests/test_mlp_parity.py); nothing of the reference's source is edited.  Returns cls."""
+    fp32 accumulation: tests/test_mlp_parity.py); nothing of the reference's source is edited.  Returns cls.
+
+    What the fused forward reads is a COPY of the two tables (`packed_tables`, grafted onto cls), rebuilt when a table's version counter
+    or address changes.  Tracked: every write through torch that bumps the counter -- an optimizer step, `load_state_dict`, `p.copy_()` /
+    any other in-place op on the parameter.  NOT tracked: a write through `param.data` (`param.data.copy_(...)`), which leaves the counter
+    alone.  torch_ema's `copy_to` / `restore` write exactly so: `install(fused_mlp=True)` wraps them (`track_derived_copies`), and any
+    other such writer has to call `model.invalidate_derived_copies()` (grafted too) itself -- without it the forward goes on reading the
+    tables as they were before the write."""
     import torch
     if getattr(cls, "_n2m_fused_field", False):
         return cls
@@ -69,6 +77,10 @@ def fuse_field(cls):
                             e.host_offsets = [int(v) for v in e.offsets.detach().cpu().tolist()]
                     if not hasattr(type(self), "packed_tables"):
                         type(self).packed_tables = _Ours.packed_tables      # the 8-byte-row copy of both tables the fused lookup gathers from
+                    if not hasattr(type(self), "invalidate_derived_copies"):
+                        type(self).invalidate_derived_copies = _Ours.invalidate_derived_copies      # ... and the way to make it forget them
+                    from nerf2mesh_amd.network import derived_copy_holders
+                    derived_copy_holders.add(self)
             except Exception:
                 ok = False
             self._n2m_fuse_ok = ok
@@ -93,6 +105,58 @@ def fuse_field(cls):
     cls._n2m_fused_field = True
     cls._n2m_reference_forward, cls._n2m_reference_density = ref_forward, ref_density
     return cls
+
+
+def track_derived_copies(ema_cls):
+    """Wrap `ema_cls.copy_to` and `ema_cls.restore` (torch_ema.ExponentialMovingAverage, or a class with its method names) so that every
+    live field one of whose hash tables is among the parameters just written forgets its derived copies
+    (`invalidate_derived_copies`): both methods write `param.data.copy_(...)`, which no version counter records.  The parameters are
+    the `parameters` argument, else what the instance tracks (`_get_parameters`, `_params` or `params`); an instance that shows neither
+    invalidates every live field (a spurious rebuild costs one pass over the tables at the next forward).  Returns ema_cls."""
+    import functools
+    if getattr(ema_cls, "_n2m_tracks_derived_copies", False):
+        return ema_cls
+
+    def written(ema, parameters):
+        if parameters is not None:
+            return parameters
+        get = getattr(ema, "_get_parameters", None)
+        if get is not None:
+            return list(get(None))
+        for name in ("_params", "params"):
+            if isinstance(getattr(ema, name, None), (list, tuple)):
+                return list(getattr(ema, name))
+        return None
+
+    def wrap(method):
+        @functools.wraps(method)
+        def wrapped(self, parameters=None):
+            if parameters is not None:
+                parameters = list(parameters)          # (a generator: the method and the scan below both walk it)
+            out = method(self, parameters)
+            from nerf2mesh_amd.network import derived_copy_holders
+            ps = written(self, parameters)
+            ids = None if ps is None else {id(p) for p in ps}
+            for model in list(derived_copy_holders):
+                if ids is None or id(model.encoder.embeddings) in ids or id(model.encoder_color.embeddings) in ids:
+                    model.invalidate_derived_copies()
+            return out
+        return wrapped
+
+    ema_cls.copy_to, ema_cls.restore = wrap(ema_cls.copy_to), wrap(ema_cls.restore)
+    ema_cls._n2m_tracks_derived_copies = True
+    return ema_cls
+
+
+def track_torch_ema():
+    """track_derived_copies on torch_ema.ExponentialMovingAverage -- the class the reference Trainer swaps the averaged weights in and out
+    with (nerf/utils.py:1250-1252) -- when that package is installed; False when it is not (nothing to wrap: no hard dependency)."""
+    try:
+        import torch_ema
+    except ImportError:
+        return False
+    track_derived_copies(torch_ema.ExponentialMovingAverage)
+    return True
 
 
 def unfuse_field(cls):

@@ -75,8 +75,11 @@ class ExponentialMovingAverage:
     @torch.no_grad()
     def copy_to(self, parameters=None):
         params = self._params if parameters is None else [p for p in parameters]
+        # p.copy_, not p.data.copy_ (the library's form): a write through `.data` leaves p._version alone, and the copies of the two hash
+        # tables the fused field gathers from (NeRFNetwork.packed_tables, GridEncoder.half_table) are keyed on it -- they would go on
+        # holding the raw tables next to the averaged MLPs.  The address stays (Adam descriptors, the exported packed buffer of peer mode).
         for s, p in zip(self.shadow_params, params):
-            p.data.copy_(s.data)
+            p.copy_(s)
 
     @torch.no_grad()
     def store(self, parameters=None):
@@ -89,11 +92,13 @@ class ExponentialMovingAverage:
             raise RuntimeError("This ExponentialMovingAverage has no `store()`ed weights to `restore()`")
         params = self._params if parameters is None else [p for p in parameters]
         for c, p in zip(self.collected_params, params):
-            p.data.copy_(c.data)
+            p.copy_(c)                     # (bumps p._version like copy_to: the derived copies are rebuilt from the restored tables)
         self.collected_params = None
 
     @contextlib.contextmanager
     def average_parameters(self, parameters=None):
+        if parameters is not None:
+            parameters = list(parameters)          # (model.parameters() is a generator: store() would leave nothing for copy_to / restore)
         self.store(parameters)
         self.copy_to(parameters)
         try:

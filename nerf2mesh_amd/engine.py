@@ -785,6 +785,9 @@ class Stage0Engine:
         else:
             L.call("n2m_adam_step", ctypes.addressof(desc), float(b1), float(b2), float(o.param_groups[0]["eps"]), _p(o.scale), _p(o.found_inf),
                    _p(o.bias), s)
+        # (the pass refreshes the packed copy; a plain fp16 copy of the colour table somebody took -- a colour-only call, an export -- is stale now and
+        #  no version counter says so: rebuilt on next use, as trainer.Stage0Trainer's shadow callback arranges it)
+        self.model.encoder_color._half_version = -1
         if fused is not None:      # behind both optimizer passes, in front of the scaler update that clears found_inf
             L.call("n2m_adam_fuse_restore", ctypes.addressof(fused), self.ho.ctypes.data, self.Lv, _p(o.found_inf), s)
             self._fuse_swap()
@@ -852,6 +855,10 @@ class Stage0Engine:
             xyzs, dirs, ts = b.samples[:3 * c], b.samples[3 * c:6 * c], b.samples[6 * c:]
         o = self.optimizer
         pk = model.packed_tables()
+        if self.lookup_overlap and getattr(self, "_packed", None) is not None and pk.data_ptr() != self._packed.data_ptr():
+            # the copy was rebuilt just now, on THIS stream (a table was written through torch since the last step: load_state_dict, the EMA
+            # swap): the lookup stream's go-ahead is an event of the last optimizer pass and does not cover it -- this step looks up in order
+            self._fine_ready = None
         sw = self.mlp_params
         e1 = model.encoder
         # seed gradient = loss scale [/ world]: gradients are SUMMED over ranks

@@ -6,6 +6,7 @@ Parameter and buffer names/shapes are the reference's (`encoder.embeddings [6119
 SURVEY.md section 8b), so a reference checkpoint's model state_dict loads with strict=True.
 """
 import math
+import weakref
 
 import torch
 import torch.nn as nn
@@ -14,6 +15,11 @@ import torch.nn.functional as F
 from .activation import trunc_exp
 from .encoding import get_encoder
 from .renderer import NeRFRenderer
+
+
+# every live field that may hold derived copies of its tables (packed_tables / half_table): what backends.track_derived_copies looks through
+# when a writer the version counters cannot see has swapped parameters
+derived_copy_holders = weakref.WeakSet()
 
 
 def x_is_cuda(net):
@@ -55,6 +61,7 @@ class NeRFNetwork(NeRFRenderer):
         self.specular_net = MLP(specular_dim + self.in_dim_dir, 3, 32, 2, bias=False)
         if self.opt.sdf:
             self.register_parameter("variance", nn.Parameter(torch.tensor(0.3, dtype=torch.float32)))
+        derived_copy_holders.add(self)
 
     def packed_tables(self):
         """[rows, 2] fp32 tensor whose 8-byte rows are {density feature fp32, colour features 2 x fp16}: the layout
@@ -80,6 +87,15 @@ class NeRFNetwork(NeRFRenderer):
                 pk.view(torch.float16)[:, 2:] = b.detach().half()
             self._packed, self._packed_key = pk, key
         return self._packed
+
+    def invalidate_derived_copies(self):
+        """Forget the packed copy and the colour encoder's fp16 copy: the next forward rebuilds them from the tables (in place where
+        `_packed_buffer` names the memory).  For writers the version counters cannot see -- `param.data.copy_(...)`, as torch_ema's
+        copy_to / restore write (backends.track_derived_copies wraps them) -- and never needed after p.copy_ / load_state_dict /
+        an optimizer step.  Costs nothing until the next forward."""
+        self._packed_key = None
+        if hasattr(self.encoder_color, "_half_version"):
+            self.encoder_color._half_version = -1
 
     def _can_fuse(self, c=None):
         # SDF: the fused kernels return the raw fp16 sigma_net output (flag bit 1); progressive levels go through max_level

@@ -97,7 +97,24 @@ def test_engine_and_trainer_update_once_per_epoch_and_evaluate_the_average():
             assert torch.equal(a, b), (cls.__name__, name)
         raw = [p.detach().clone() for p in tr.model.parameters()]
         p_ema, p_raw = tr.eval_psnr(cam=0, use_ema=True), tr.eval_psnr(cam=0)
-        assert p_ema == p_ema and p_raw == p_raw and p_ema != p_raw            # finite, and the averaged weights really were rendered
+        assert p_ema == p_ema and p_raw == p_raw                                # finite
+        # ... and the averaged weights really were rendered, ALL of them: the same number as a trainer whose model was loaded with the shadow
+        # weights gives (its copies of the hash tables are built from scratch), and not the number of the hybrid a stale copy amounts to --
+        # averaged MLPs over the raw tables (tests/test_derived_copies.py)
+        state = {k: v.detach().clone() for k, v in tr.model.state_dict().items()}
+        hybrid = dict(state)
+        for name, s in zip(names, tr.ema.shadow_params):
+            state[name] = s.detach().clone()
+            if name not in ("encoder.embeddings", "encoder_color.embeddings"):
+                hybrid[name] = s.detach().clone()
+        psnr_of = {}
+        for which, sd in (("averaged", state), ("hybrid", hybrid)):
+            other = cls(NeRFNetwork(opt), opt, synthetic.make_cameras(6, seed=0), dev, seed=0)
+            other.model.load_state_dict(sd)
+            psnr_of[which] = other.eval_psnr(cam=0)
+            del other
+        assert p_ema == psnr_of["averaged"], (cls.__name__, p_ema, psnr_of)
+        assert p_ema != psnr_of["hybrid"] and p_ema != p_raw, (cls.__name__, p_ema, p_raw, psnr_of)
         for p, b in zip(tr.model.parameters(), raw):                              # ... and taken out again
             assert torch.equal(p.detach(), b)
         tr.train_step()                                                           # the step still runs on the restored weights

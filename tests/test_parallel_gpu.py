@@ -136,6 +136,16 @@ def test_peer_store_with_a_rank_without_samples():
 
 
 @pytest.mark.gpu
+def test_peer_store_evaluates_the_average_inside_the_exported_buffer():
+    """The averaged weights in and out between two steps of the peer-store exchange (tools/dist_check.py, N2M_DIST_EMA_EVAL): the EMA swap writes
+    with p.copy_, so the packed copy is rebuilt -- into the buffer the other rank stores its rows into, not into a new tensor ("the packed
+    table left the exported buffer") -- holds the shadow tables under the average and the raw ones after it, and the two steps behind it
+    leave the replicas bit-identical."""
+    line = _dist_check(29577, 24, {"N2M_SHARD_ADAM": "1", "N2M_PEER_STORE": "1", "N2M_DIST_EMA_EVAL": "1"})
+    assert "peer_store=True" in line and "ema_eval=True" in line, line
+
+
+@pytest.mark.gpu
 def test_peer_store_primitives_and_timeout():
     """n2m_peer_* between two processes on one GPU (tools/peer_check.py): a buffer one process allocates is written by the other through
     the mapped pointer; signal / wait hand over in both directions; the slot sum is the rank-order sum; a wait for a signal that never

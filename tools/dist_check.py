@@ -47,6 +47,28 @@ for it in range(steps):
             tr.model.density_grid.mul_(1.0)
         else:
             tr.model.density_grid[0, 0] = -1.0                # Morton cell 0 = the (-1,-1,-1) corner: empty, its bit is 0 either way
+ema_ok = True
+if os.environ.get("N2M_DIST_EMA_EVAL") and ENGINE:
+    # every rank, at the same step: one EMA update, the averaged weights in and out (tests/test_parallel_gpu.py).  Under the average the packed
+    # copy holds the shadow tables, afterwards the raw ones again -- in the SAME memory where peers store into it (peer-store mode) -- and the
+    # steps behind it run as before
+    tr.ema_update()
+    names = [n for n, p in tr.model.named_parameters() if p.requires_grad]
+    shadow = dict(zip(names, tr.ema.shadow_params))
+    e1, e2 = tr.model.encoder.embeddings, tr.model.encoder_color.embeddings
+
+    def copies_hold(t1, t2):
+        pk = tr.model.packed_tables()
+        return (torch.equal(pk[:, 0], t1.detach()[:, 0]) and torch.equal(pk.view(torch.float16)[:, 2:], t2.detach().half())
+                and (getattr(tr, "peer", None) is None or pk.data_ptr() == tr.peer.packed.data_ptr()))
+
+    with tr.averaged_parameters():
+        ema_ok = copies_hold(shadow["encoder.embeddings"], shadow["encoder_color.embeddings"]) and torch.equal(e1.detach(), shadow["encoder.embeddings"])
+    ema_ok = ema_ok and copies_hold(e1, e2) and not torch.equal(e1.detach(), shadow["encoder.embeddings"])
+    p_avg = tr.eval_psnr(cam=0, downscale=8, use_ema=True)
+    ema_ok = ema_ok and p_avg == p_avg and copies_hold(e1, e2)
+    for _ in range(2):
+        losses.append(float(tr.train_step()))
 if hasattr(tr, "sync_parameters"):
     tr.sync_parameters()              # sharded optimizer: every rank owns 1/W of the table rows until the fp32 tensors are gathered
 torch.cuda.synchronize()
@@ -59,7 +81,7 @@ if rank == 0 and os.environ.get("N2M_DIST_DUMP_GRID"):     # occupancy state: bi
     torch.save({"bits": tr.model.density_bitfield.cpu(), "grid": tr.model.density_grid.cpu()}, os.environ["N2M_DIST_DUMP_GRID"])
 if rank == 0 and os.environ.get("N2M_DIST_DUMP"):          # every 97th parameter, for run-to-run comparisons (tests/test_parallel_gpu.py)
     torch.save(flat[::97].cpu(), os.environ["N2M_DIST_DUMP"])
-ok = torch.isfinite(flat).all().item() and all(l == l for l in losses)
+ok = torch.isfinite(flat).all().item() and all(l == l for l in losses) and ema_ok
 if world > 1:
     gathered = [torch.zeros_like(digest) for _ in range(world)]
     dist.all_gather(gathered, digest)
@@ -86,7 +108,7 @@ if os.environ.get("N2M_DIST_CKPT"):
     if world > 1:
         dist.barrier()
 if rank == 0:
-    print(f"DIST_CHECK {'OK' if ok else 'FAILED'} driver={type(tr).__name__} shard={getattr(tr, 'shard', False)} peer_store={getattr(tr, 'peer', None) is not None} refresh_sharded={bool(getattr(tr.model, 'refresh_shard', None)) and bool((getattr(tr.model, '_refresh_bufs', None) or {}).get('shard_ok'))} backend={dist.get_backend() if world > 1 else 'none'} world={world} steps={steps} loss {first:.5f} -> {last:.5f} digest={[float(x) for x in digest]}")
+    print(f"DIST_CHECK {'OK' if ok else 'FAILED'} driver={type(tr).__name__} shard={getattr(tr, 'shard', False)} peer_store={getattr(tr, 'peer', None) is not None} refresh_sharded={bool(getattr(tr.model, 'refresh_shard', None)) and bool((getattr(tr.model, '_refresh_bufs', None) or {}).get('shard_ok'))} ema_eval={bool(os.environ.get('N2M_DIST_EMA_EVAL')) and ENGINE and ema_ok} backend={dist.get_backend() if world > 1 else 'none'} world={world} steps={steps} loss {first:.5f} -> {last:.5f} digest={[float(x) for x in digest]}")
 if world > 1:
     dist.destroy_process_group()
 sys.exit(0 if ok else 1)
