@@ -101,6 +101,27 @@ int n2m_laplacian_backward_acc(const float* Lv, const float* norm, const int32_t
                                float lam_lap, const float* offsets, float w_in, float w_out, uint32_t n_in, float* d_verts, float* found_inf,
                                void* stream);
 
+/* Normal-consistency and edge-length losses of the mesh, pytorch3d's `mesh_normal_consistency` / `mesh_edge_loss` as nerf/utils.py:759-769
+ * calls them (one mesh, target edge length 0), on a topology built once per mesh (trainer.MeshEdgeTerms):
+ *   edges [E, 2] int32: the unique undirected edges, v0 < v1;  pairs [P, 4] int32 (16-byte aligned): (v0, v1, a, b) for every pair of faces
+ *   on an edge (an edge with k faces gives k (k - 1) / 2), v0 < v1 the edge's endpoints, a / b the vertices opposite it in the two faces.
+ *   Per pair, with e = v1 - v0, n0 = e x (a - v0), n1 = -(e x (b - v0)): 1 - n0 . n1 / (max(|n0|, 1e-8) max(|n1|, 1e-8)); per edge |v0 - v1|^2.
+ * forward: partial [ceil(P / 256) + ceil(E / 256)] = per-workgroup sums of w_normal * (pair term), then of w_edge * (edge term), in a fixed
+ *   order: value = sum(partial).  The caller folds 1 / P, 1 / E and the loss weights into w_normal / w_edge.
+ * backward: d_verts [V, 3] = grad (device scalar) times the gradient of that value.  One thread per vertex walks two CSRs (pair_ptr / edge_ptr
+ *   [V + 1]; pair_ref = 4 * pair + corner, edge_ref = 2 * edge + corner of every term the vertex takes part in, ascending) and recomputes each
+ *   term's gradient for its corner: a fixed summation order, no atomics.  Where a norm is below 1e-8 the gradient is that of the clamped
+ *   expression (finite for a zero-area face), as torch's is.  _acc ADDS the result onto d_verts.
+ * P = 0 leaves the pair arrays unread (they may be NULL), E = 0 the edge arrays; with P = E = 0 or V = 0 nothing is launched or written. */
+int n2m_mesh_losses_forward(const float* verts, const int32_t* pairs, uint32_t P, const int32_t* edges, uint32_t E, float w_normal, float w_edge,
+                            float* partial, void* stream);
+int n2m_mesh_losses_backward(const float* verts, const int32_t* pairs, const int32_t* pair_ptr, const int32_t* pair_ref, uint32_t P,
+                             const int32_t* edges, const int32_t* edge_ptr, const int32_t* edge_ref, uint32_t E, uint32_t V, const float* grad,
+                             float w_normal, float w_edge, float* d_verts, void* stream);
+int n2m_mesh_losses_backward_acc(const float* verts, const int32_t* pairs, const int32_t* pair_ptr, const int32_t* pair_ref, uint32_t P,
+                                 const int32_t* edges, const int32_t* edge_ptr, const int32_t* edge_ref, uint32_t E, uint32_t V, const float* grad,
+                                 float w_normal, float w_edge, float* d_verts, void* stream);
+
 /* Rows of a [N, C] fp32 array by index -- the boolean-mask gather / scatter around the shading of a stage-1 frame (nerf/renderer.py:864,
  * 875-881: `xyzs[mask]`, `rgbs[mask] = ...`) once the covered pixels are an index list: out[k, :] = x[idx[k], :] and dst[idx[k], :] = src[k, :]
  * (idx int64 [K], unique for the scatter; rows of dst that are not listed keep their value). */

@@ -173,6 +173,9 @@ SIGNATURES = {
     "n2m_laplacian_forward": [_vp, _vp, _vp, _u32, _vp, _f32, _f32, _f32, _u32, _vp, _vp, _vp, _vp],
     "n2m_laplacian_backward": [_vp, _vp, _vp, _vp, _u32, _vp, _f32, _vp, _f32, _f32, _u32, _vp, _vp, _vp],
     "n2m_laplacian_backward_acc": [_vp, _vp, _vp, _vp, _u32, _vp, _f32, _vp, _f32, _f32, _u32, _vp, _vp, _vp],
+    "n2m_mesh_losses_forward": [_vp, _vp, _u32, _vp, _u32, _f32, _f32, _vp, _vp],
+    "n2m_mesh_losses_backward": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _f32, _f32, _vp, _vp],
+    "n2m_mesh_losses_backward_acc": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _f32, _f32, _vp, _vp],
     "n2m_gather_rows": [_vp, _vp, _u32, _u32, _vp, _vp],
     "n2m_gather_rows_strided": [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp],
     "n2m_scatter_rows_strided": [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp],

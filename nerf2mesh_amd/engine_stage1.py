@@ -9,7 +9,8 @@ as a FIXED SEQUENCE OF C-ABI CALLS on preallocated buffers -- no autograd graph,
   -> n2m_antialias_backward -> n2m_gather_rows (colour gradient of the covered pixels) -> n2m_field_backward
   -> n2m_grid_encode_backward_binned_pair (colour table alone, overwrite mode, fp16 gradient)
   -> n2m_scatter_rows (coverage gradient) -> n2m_interpolate_backward -> n2m_rasterize_backward (onto the antialias' vertex gradient)
-  -> n2m_to_clip_backward -> n2m_laplacian_forward / _backward (smoothness + offset penalty) -> FusedAdamAMP.step
+  -> n2m_to_clip_backward -> [lambda_normal / lambda_edgelen > 0: n2m_mesh_losses_forward / _backward_acc]
+  -> n2m_laplacian_forward / _backward (smoothness + offset penalty) -> FusedAdamAMP.step
 
 Every kernel is the one the autograd path launches, fed the same inputs; what differs is fp32 association in two sums (the two clip-space
 gradients land in one buffer, the three vertex gradients are added in a fixed order) -- tests/test_stage1.py holds the executor to the
@@ -60,8 +61,16 @@ class Stage1Engine:
         self.d_rast = f(self.h, self.w, 4)
         self.image, self.depth, self.ws, self.trig, self.loss_px = f(N, 3), f(N), f(N), f(N), f(N)
         nb_head, nb_reg = (N + 255) // 256, (V + 255) // 256
-        self.partials = f(nb_head + nb_reg)                # [image head's | regularisers'] workgroup sums: ONE reduction gives the step's loss
-        self.partial, self.reg_partial = self.partials[:nb_head], self.partials[nb_head:]
+        # normal-consistency / edge-length losses (trainer.MeshEdgeTerms; None with both weights 0: no launch, no buffer): a weight of 0 drops
+        # its terms from the launches
+        self.mesh = tr.mesh_terms
+        self.mesh_pe, nb_mesh = (0, 0), 0
+        if self.mesh is not None:
+            self.mesh_pe = (self.mesh.n_pairs if opt.lambda_normal > 0 else 0, self.mesh.n_edges if opt.lambda_edgelen > 0 else 0)
+            nb_mesh = (self.mesh_pe[0] + 255) // 256 + (self.mesh_pe[1] + 255) // 256
+        self.partials = f(nb_head + nb_reg + nb_mesh)      # [image head's | regularisers' | mesh losses'] workgroup sums: ONE reduction gives the step's loss
+        self.partial, self.reg_partial = self.partials[:nb_head], self.partials[nb_head:nb_head + nb_reg]
+        self.mesh_partial = self.partials[nb_head + nb_reg:] if nb_mesh else None
         self.half = torch.tensor(0.5, dtype=torch.float32, device=dev)
         self.zero = torch.zeros((), dtype=torch.float32, device=dev)
         self.cap = 0
@@ -221,6 +230,15 @@ class Stage1Engine:
                 if self.world > 1:
                     tok = tr.sync.all_reduce_sum_begin([self.g2], [self.dw])
             L.call("n2m_to_clip_backward", _p(self.d_clip), _p(mvp), V, _p(self.d_verts), s)
+            Npx = float(h0 * w0)
+            if self.mesh_partial is not None:
+                # ---- normal consistency + edge length (nerf/utils.py:759-769): value (weights x h0 w0, like the regularisers' below) and the
+                # gradient added onto the rendering gradient; the non-finite check at the tail of n2m_laplacian_backward_acc covers it
+                mt, (P, E) = self.mesh, self.mesh_pe
+                w_n, w_e = mt.weights(max(opt.lambda_normal, 0.0), max(opt.lambda_edgelen, 0.0))
+                L.call("n2m_mesh_losses_forward", _p(self.verts), _p(mt.pairs), P, _p(mt.edges), E, w_n * Npx, w_e * Npx, _p(self.mesh_partial), s)
+                L.call("n2m_mesh_losses_backward_acc", _p(self.verts), _p(mt.pairs), _p(mt.pair_ptr), _p(mt.pair_ref), P, _p(mt.edges), _p(mt.edge_ptr),
+                       _p(mt.edge_ref), E, V, _p(self.seed), w_n, w_e, _p(self.d_verts), s)
             # ---- mesh regularisers (nerf/utils.py:761-789): value and gradient, the gradient scaled like everything else
             off = model.vertices_offsets.detach()
             n_in = int(model.v_cumsum[1]) if opt.bound > 1 else None
@@ -229,7 +247,6 @@ class Stage1Engine:
             else:
                 w_in, w_out = float(opt.lambda_offsets) / n_in, 0.1 * float(opt.lambda_offsets) / (V - n_in)
             lap = tr.laplacian
-            Npx = float(h0 * w0)
             # the VALUE's weights carry a factor h0 w0, so that (image-head sums + regulariser sums) / (h0 w0) is the loss in one reduction
             L.call("n2m_laplacian_forward", _p(self.verts), _p(lap.row_ptr), _p(lap.col), V, _p(off), float(opt.lambda_lap) * Npx, w_in * Npx, w_out * Npx, n_in,
                    _p(self.Lv), _p(self.norm), _p(self.reg_partial), s)

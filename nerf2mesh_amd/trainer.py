@@ -434,6 +434,103 @@ class _MeshRegularisers(torch.autograd.Function):
         return d, d_off, None, None, None, None, None, None
 
 
+class MeshEdgeTerms:
+    """Normal-consistency and edge-length losses of the mesh, pytorch3d's `mesh_normal_consistency` / `mesh_edge_loss` as nerf/utils.py:759-769
+    calls them (ONE mesh -- model.triangles, all cascades concatenated -- and target edge length 0):
+
+      normal:  mean over all pairs of faces that share an edge of 1 - cos(n0, n1), with e = v1 - v0 along the edge (v0 < v1: the sorted edge, not
+               either face's winding, so the value does not depend on the winding), n0 = e x (a - v0), n1 = -(e x (b - v0)), a / b the
+               vertices opposite the edge in the two faces, cos = torch.cosine_similarity (each norm clamped at 1e-8); 0 without pairs
+      edge:    mean over the unique edges of |v0 - v1|^2; 0 without edges
+
+    The topology depends on the faces only and is built once per mesh from torch ops on their device: `edges` [E, 2] i32, `pairs` [P, 4] i32
+    (v0, v1, a, b; an edge with k faces gives k (k - 1) / 2 pairs, faces in ascending order -- non-manifold edges are legal after a refinement,
+    boundary edges give none) and, for the gather-form backward (n2m_mesh_losses_backward), one CSR each from a vertex to the pair / edge terms
+    it takes part in: `pair_ref` = 4 * pair + corner, `edge_ref` = 2 * edge + corner, ascending within a row -- a fixed summation order."""
+
+    def __init__(self, faces, n_verts):
+        from .mesh_simplify import _edges, _offsets
+        V = self.n_verts = int(n_verts)
+        f = faces.long()
+        dev = f.device
+        if f.shape[0] == 0:           # no face: no term
+            edges, cnt, c2e = (torch.zeros(s, dtype=torch.int32, device=dev) for s in ((0, 2), (0,), (0, 3)))
+        else:
+            edges, cnt, c2e = _edges(f, V)
+        self.edges = edges
+        # half-edges (face, corner k) -> edge (v_k, v_k+1), opposite vertex v_k+2; grouped by edge, faces ascending within an edge
+        eid, order = torch.sort(c2e.reshape(-1).long(), stable=True)
+        opp = f.roll(-2, dims=1).reshape(-1)[order]
+        cnt = cnt.long()
+        later = cnt[eid] - 1 - (torch.arange(eid.numel(), device=dev) - (cnt.cumsum(0) - cnt)[eid])      # faces behind this one on its edge
+        first = torch.repeat_interleave(torch.arange(eid.numel(), device=dev), later)                    # (the one host read: P)
+        second = first + 1 + torch.arange(first.numel(), device=dev) - (later.cumsum(0) - later)[first]
+        e = edges.long()[eid[first]]
+        self.pairs = torch.stack([e[:, 0], e[:, 1], opp[first], opp[second]], 1).to(torch.int32).contiguous().view(-1, 4)
+        self.n_edges, self.n_pairs = int(edges.shape[0]), int(self.pairs.shape[0])
+
+        def csr(table):           # entries sorted by vertex, then by (term, corner): the flat index of `table` IS width * term + corner
+            keys, ref = torch.sort(table.reshape(-1).long(), stable=True)
+            return _offsets(keys, V), ref.to(torch.int32).contiguous()
+        self.pair_ptr, self.pair_ref = csr(self.pairs)
+        self.edge_ptr, self.edge_ref = csr(self.edges)
+
+    def weights(self, lam_normal, lam_edge):
+        """(w_normal, w_edge) of the kernels: the loss weights over the number of terms (0 where there are none)."""
+        return (float(lam_normal) / self.n_pairs if self.n_pairs else 0.0, float(lam_edge) / self.n_edges if self.n_edges else 0.0)
+
+    def __call__(self, verts, lam_normal=1.0, lam_edge=1.0):
+        """lam_normal * normal consistency + lam_edge * edge length of `verts` [V, 3] as one value."""
+        if verts.is_cuda and verts.dtype == torch.float32:
+            return _MeshLosses.apply(verts, self, *self.weights(lam_normal, lam_edge))
+        return lam_normal * self.normal_consistency(verts) + lam_edge * self.edge_length(verts)
+
+    def normal_consistency(self, verts):
+        """The torch form (any device, any float dtype)."""
+        if self.n_pairs == 0:
+            return verts.sum() * 0.0
+        v0, v1, a, b = (verts[self.pairs[:, k].long()] for k in range(4))
+        e = v1 - v0
+        n0, n1 = torch.cross(e, a - v0, dim=1), -torch.cross(e, b - v0, dim=1)
+        c = ((n0 / n0.norm(dim=1, keepdim=True).clamp_min(1e-8)) * (n1 / n1.norm(dim=1, keepdim=True).clamp_min(1e-8))).sum(1)
+        return (1 - c).mean()
+
+    def edge_length(self, verts):
+        if self.n_edges == 0:
+            return verts.sum() * 0.0
+        e = self.edges.long()
+        return ((verts[e[:, 0]] - verts[e[:, 1]]) ** 2).sum(1).mean()
+
+
+class _MeshLosses(torch.autograd.Function):
+    """w_normal * sum of the pair terms + w_edge * sum of the edge terms through n2m_mesh_losses_forward / _backward.  A weight of 0 drops its
+    terms from both launches; with nothing left nothing is launched, the value is 0 and so is the gradient."""
+
+    @staticmethod
+    def forward(ctx, verts, terms, w_normal, w_edge):
+        from . import _lib as L
+        verts = verts.contiguous()
+        P, E = terms.n_pairs if w_normal != 0 else 0, terms.n_edges if w_edge != 0 else 0
+        partial = torch.empty((P + 255) // 256 + (E + 255) // 256, dtype=torch.float32, device=verts.device)
+        L.call("n2m_mesh_losses_forward", L.ptr(verts), L.ptr(terms.pairs), P, L.ptr(terms.edges), E, w_normal, w_edge, L.ptr(partial), L.stream())
+        ctx.save_for_backward(verts)
+        ctx.terms, ctx.args = terms, (P, E, w_normal, w_edge)
+        return partial.sum()
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib as L
+        verts, = ctx.saved_tensors
+        t, (P, E, w_normal, w_edge) = ctx.terms, ctx.args
+        if P == 0 and E == 0:
+            return torch.zeros_like(verts), None, None, None
+        g = g.float().contiguous()
+        d = torch.empty_like(verts)
+        L.call("n2m_mesh_losses_backward", L.ptr(verts), L.ptr(t.pairs), L.ptr(t.pair_ptr), L.ptr(t.pair_ref), P, L.ptr(t.edges), L.ptr(t.edge_ptr),
+               L.ptr(t.edge_ref), E, verts.shape[0], L.ptr(g), w_normal, w_edge, L.ptr(d), L.stream())
+        return d, None, None, None
+
+
 class _NeighbourSum(torch.autograd.Function):
     """nb[i] = sum_{j in N(i)} v[j] over a SYMMETRIC directed edge list (i,j) and (j,i) both present: the adjoint is the same
     operator, so backward is another gather + index_add instead of autograd's sort-based index_put of the gather's backward
@@ -506,6 +603,8 @@ class Stage1Trainer:
         jj, ii = torch.meshgrid(torch.arange(H, device=device), torch.arange(W, device=device), indexing="ij")
         self.pix = (jj * W + ii).reshape(-1)
         self.laplacian = UniformLaplacian(model.triangles, model.vertices.shape[0])
+        # normal-consistency / edge-length losses (nerf/utils.py:759-769): their topology is built only when one of them is on
+        self.mesh_terms = MeshEdgeTerms(model.triangles, model.vertices.shape[0]) if opt.lambda_normal > 0 or opt.lambda_edgelen > 0 else None
         self.view_cache = {}          # per view: rays + ground-truth RGBA, resident in HBM like the reference's --preload
         self._dirs = {}               # per view: unit directions at the ssaa resolution (30 MB per 800 x 800 view at ssaa 2)
         self.covered_seen = 0         # shaded (covered) full-resolution pixels so far: the unit of the stage-1 byte model
@@ -629,6 +728,9 @@ class Stage1Trainer:
             reg_done = False
         if opt.lambda_lap > 0 and not reg_done:
             loss = loss + opt.lambda_lap * self.laplacian(verts if verts is not None else model.vertices + model.vertices_offsets)
+        if self.mesh_terms is not None:                                      # nerf/utils.py:759-769, on the same vertices as the Laplacian
+            loss = loss + self.mesh_terms(verts if verts is not None else model.vertices + model.vertices_offsets,
+                                          max(opt.lambda_normal, 0.0), max(opt.lambda_edgelen, 0.0))
         if opt.lambda_offsets > 0 and not reg_done:                          # nerf/utils.py:772-789
             off = model.vertices_offsets
             if opt.bound > 1:       # inner mesh (cascade 0) + 0.1 x the outer cascades' meshes
