@@ -790,6 +790,23 @@ int n2m_batch_rays_cnf(const float* poses, const float* uniforms, uint32_t V, ui
                        float cy, const float* images, const float* aabb, float min_near, float* rays_o, float* rays_d, float* rgba,
                        float* nears, float* fars, float* noises, float* bg, int32_t* counter, const float* cam_near_far, void* stream);
 
+/* Captured image sets (csrc/capture.hip, nerf2mesh_amd/capture.py).  bank: [V, H*W] packed RGBA8 words, R in the low byte (the reference's
+ * uint8 image bank, nerf/provider.py:237; a 3-channel source stores alpha 255); lut: [2,256] f32 decode table built on the host (row 0: R, G,
+ * B -- x / 255, or srgb_to_linear of it under --color_space linear, nerf/provider.py:323-325 --, row 1: alpha = x / 255).
+ * n2m_batch_rays_u8: n2m_batch_rays_cnf with the ground truth gathered from the bank (same arithmetic, same operand order otherwise). */
+int n2m_batch_rays_u8(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy, float cx,
+                      float cy, const uint32_t* bank, const float* lut, const float* aabb, float min_near, float* rays_o, float* rays_d,
+                      float* rgba, float* nears, float* fars, float* noises, float* bg, int32_t* counter, const float* cam_near_far,
+                      void* stream);
+/* One whole view at pixel stride `stride`: h = H / stride, w = W / stride, output pixel (y, x) = source pixel (y stride, x stride); rays_o,
+ * rays_d [h*w,3], rgba [h*w,4] f32.  dirs (may be NULL): [h*ssaa * w*ssaa, 3] unit directions, every pixel's safe_normalize(d) repeated
+ * ssaa x ssaa times (nearest upscale, nerf/renderer.py:821-828). */
+int n2m_capture_view(const float* poses, uint32_t V, uint32_t view, uint32_t H, uint32_t W, uint32_t stride, float fx, float fy, float cx,
+                     float cy, const uint32_t* bank, const float* lut, float* rays_o, float* rays_d, float* rgba, float* dirs, uint32_t ssaa,
+                     void* stream);
+/* k x k integer box mean of every channel, (sum + k*k/2) / (k*k); src [V,H,W] words -> dst [V,H/k,W/k]; partial blocks are dropped. */
+int n2m_capture_box_downscale(const uint32_t* src, uint32_t V, uint32_t H, uint32_t W, uint32_t k, uint32_t* dst, void* stream);
+
 /* Photometric loss head of the stage-0 step in one launch per direction:
  *   pred   = image + (1 - weights_sum) * bg                      nerf/renderer.py:747
  *   target = gt.rgb * gt.a + bg * (1 - gt.a)                     nerf/utils.py:663-664

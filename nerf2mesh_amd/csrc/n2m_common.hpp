@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <hip/hip_ext.h>
+#include <float.h>
 #include <stdint.h>
 #include <stdio.h>
 
@@ -136,4 +137,27 @@ __device__ __forceinline__ uint32_t n2m_wave_sum_u32(uint32_t v) {
 __device__ __forceinline__ float n2m_lane63(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63)); }
 __device__ __forceinline__ float n2m_lane_below(float v, float first) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, first), __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
+}
+
+// slab test of one ray (raymarching.cu:91-145): (near, far), both FLT_MAX on a miss (shared by raymarching.hip and capture.hip)
+__device__ __forceinline__ void n2m_near_far_of(const float (&o)[3], const float (&d)[3], const float* __restrict__ aabb, float min_near,
+                                            float& near, float& far) {
+    float tn = 0.f, tf = 0.f;
+    bool hit = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        if (!hit) break;
+        const float inv = 1.0f / d[a];
+        const float org = o[a];
+        float lo = (aabb[a] - org) * inv, hi = (aabb[a + 3] - org) * inv;
+        if (lo > hi) { const float t = lo; lo = hi; hi = t; }
+        if (a == 0) { tn = lo; tf = hi; continue; }
+        if (tn > hi || lo > tf) { hit = false; break; }
+        if (lo > tn) tn = lo;
+        if (hi < tf) tf = hi;
+    }
+    if (!hit) { near = FLT_MAX; far = FLT_MAX; return; }
+    if (tn < min_near) tn = min_near;
+    near = tn;
+    far = tf;
 }

@@ -25,36 +25,13 @@ constexpr float kSqrt3 = 1.7320508075688772f;
 
 // ------------------------------------------------------------------------------------------- small kernels
 
-// slab test of one ray (raymarching.cu:91-145): (near, far), both FLT_MAX on a miss
-__device__ __forceinline__ void near_far_of(const float (&o)[3], const float (&d)[3], const float* __restrict__ aabb, float min_near,
-                                            float& near, float& far) {
-    float tn = 0.f, tf = 0.f;
-    bool hit = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (!hit) break;
-        const float inv = 1.0f / d[a];
-        const float org = o[a];
-        float lo = (aabb[a] - org) * inv, hi = (aabb[a + 3] - org) * inv;
-        if (lo > hi) { const float t = lo; lo = hi; hi = t; }
-        if (a == 0) { tn = lo; tf = hi; continue; }
-        if (tn > hi || lo > tf) { hit = false; break; }
-        if (lo > tn) tn = lo;
-        if (hi < tf) tf = hi;
-    }
-    if (!hit) { near = FLT_MAX; far = FLT_MAX; return; }
-    if (tn < min_near) tn = min_near;
-    near = tn;
-    far = tf;
-}
-
 __global__ void near_far_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                 const float* __restrict__ aabb, uint32_t N, float min_near,
                                 float* __restrict__ nears, float* __restrict__ fars) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;
     const float o[3] = {rays_o[3 * n], rays_o[3 * n + 1], rays_o[3 * n + 2]}, d[3] = {rays_d[3 * n], rays_d[3 * n + 1], rays_d[3 * n + 2]};
-    near_far_of(o, d, aabb, min_near, nears[n], fars[n]);
+    n2m_near_far_of(o, d, aabb, min_near, nears[n], fars[n]);
 }
 
 // A whole training batch from ONE tensor of uniforms u [N,6] in [0,1): view = floor(u0 V), pixel = floor(u1 H W) (random_image_batch,
@@ -86,7 +63,7 @@ batch_rays_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __re
     }
     *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = *reinterpret_cast<const float4*>(images + ((size_t)v * HW + (size_t)p) * 4);
     float tn, tf;
-    near_far_of(o, d, aabb, min_near, tn, tf);
+    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
     if (cam_near_far) {       // per-view clamp from the sparse points (nerf/renderer.py:689-691, colmap_provider.py:563-565): maximum / minimum
         tn = fmaxf(tn, cam_near_far[2 * v]);
         tf = fminf(tf, cam_near_far[2 * v + 1]);

@@ -82,9 +82,15 @@ class _RayBufs:
 
 
 class Stage0Engine:
-    def __init__(self, model, opt, poses, device, rank=0, world_size=1, seed=0, ema_decay=0.95):
+    def __init__(self, model, opt, poses, device, rank=0, world_size=1, seed=0, ema_decay=0.95, capture=None):
         self.model, self.opt, self.device = model.to(device), opt, torch.device(device)
         dev = self.device
+        # capture (capture.Capture, opt-in): a captured image set instead of the analytic box scene -- its poses, its intrinsics, its uint8
+        # bank (n2m_batch_rays_u8 in the place of n2m_batch_rays_cnf), its per-view depth ranges.  None: everything as it was.
+        self.capture = capture
+        if capture is not None:
+            capture.check_device(dev)
+            poses = capture.poses
         assert dev.type == "cuda", "the step executor drives HIP kernels: no CPU path"
         if bool(opt.sdf) and world_size > 1:
             raise ValueError("Stage0Engine runs the SDF recipe on one rank; use trainer.Stage0Trainer for multi-rank SDF training")
@@ -113,6 +119,8 @@ class Stage0Engine:
         self.boxes = synthetic.boxes(dev, self.scene)
         # --enable_cam_near_far (main.py:40, config 4): per-view (near, far) from the sparse points, applied by the batch kernel
         self.cam_near_far = synthetic.cam_near_far(self.poses, self.scene) if getattr(opt, "enable_cam_near_far", False) else None
+        if capture is not None:
+            self.cam_near_far = capture.cam_near_far
         self.samples_seen = self.rays_seen = 0
         self.last_num_points = 0
         self._loss_pending, self._loss_sum = [], torch.zeros(1, device=dev)
@@ -311,8 +319,16 @@ class Stage0Engine:
     def loss_acc(self):
         return self._loss_sum
 
+    def _lambda_mask(self):
+        """Weight of the mask term; 0 for a capture without an alpha channel (the reference skips the term for 3-channel images, nerf/utils.py:681)."""
+        if self.capture is not None and not self.capture.has_alpha:
+            return 0.0
+        return float(max(self.opt.lambda_mask, 0.0))
+
     def mark_untrained(self):
-        if self.opt.mark_untrained:
+        if self.opt.mark_untrained and self.capture is not None:
+            self.model.mark_untrained_grid(self.poses, self.capture.intrinsics, cam_near_far=self.cam_near_far)
+        elif self.opt.mark_untrained:
             f = synthetic.LEGO_FOCAL
             self.model.mark_untrained_grid(self.poses, (f, f, synthetic.LEGO_HW / 2, synthetic.LEGO_HW / 2), cam_near_far=self.cam_near_far)
 
@@ -373,7 +389,8 @@ class Stage0Engine:
         """Batch of N rays: pixel choice, rays + ground truth, near/far, march pass 1 (count + offset scan), count on its way to the host.
         Reads the cameras, the images and the occupancy bit field only."""
         opt, model, dev = self.opt, self.model, self.device
-        if self.images is None:
+        cap = self.capture
+        if cap is None and self.images is None:
             self.images = synthetic.preload_images(self.poses, self.boxes)
         b = self._ray_bufs(N)
         b.N, b.M = N, None
@@ -382,8 +399,13 @@ class Stage0Engine:
         b.u = torch.rand(N, 6, device=dev, generator=self.gen)
         self._aabb = model.aabb_train
         b.bg = b.bg_buf if opt.background != "white" else None
-        synthetic.batch_from_uniforms(self.poses, self.images, b.u, self._aabb, model.min_near,
-                                      out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg), counter=b.counter, cam_near_far=self.cam_near_far)
+        if cap is not None:
+            from .capture import batch_from_uniforms_u8
+            batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, b.u, self._aabb, model.min_near, cap.H, cap.W, cap.intrinsics,
+                                   out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg), counter=b.counter, cam_near_far=self.cam_near_far)
+        else:
+            synthetic.batch_from_uniforms(self.poses, self.images, b.u, self._aabb, model.min_near,
+                                          out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg), counter=b.counter, cam_near_far=self.cam_near_far)
         bits = model.density_bitfield
         b.args = (_p(b.o), _p(b.d), _p(bits), float(model.real_bound), int(bool(opt.contract)), float(opt.dt_gamma), int(opt.max_steps), N,
                   int(model.cascade), int(model.grid_size), _p(b.nears), _p(b.fars))
@@ -930,7 +952,7 @@ class Stage0Engine:
             if want_tv and self.tv_at == 1:
                 start_tv()
         bg_t, bg_s = (bg, 0.0) if random_bg else (None, 1.0)
-        lam_rgb, lam_mask = float(opt.lambda_rgb), float(max(opt.lambda_mask, 0.0))
+        lam_rgb, lam_mask = float(opt.lambda_rgb), self._lambda_mask()
         # ---- compositing + loss head + both backward passes: one launch (seed gradient = loss scale [/ world]: gradients are SUMMED over ranks)
         early = None
         d_sigma, d_rgb = w["d_sr"][:max(M, 1)], w["d_sr"][max(M, 1):4 * max(M, 1)]
@@ -1136,7 +1158,7 @@ class Stage0Engine:
         eps, car = float(opt.normal_anneal_epsilon), float(opt.cos_anneal_ratio)
         random_bg = b.bg is not None
         bg_t, bg_s = (b.bg, 0.0) if random_bg else (None, 1.0)
-        lam_rgb, lam_mask = float(opt.lambda_rgb), float(max(opt.lambda_mask, 0.0))
+        lam_rgb, lam_mask = float(opt.lambda_rgb), self._lambda_mask()
         sb = self._sdf_buf(M)
         d_sigma, d_rgb = w["d_sr"][:max(M, 1)], w["d_sr"][max(M, 1):4 * max(M, 1)]
         extra = extra2 = None
@@ -1285,11 +1307,12 @@ class Stage0Engine:
         return self.ema.average_parameters()
 
     @torch.no_grad()
-    def eval_psnr(self, cam=0, downscale=4, use_ema=False):
-        """use_ema: evaluate the averaged weights, as the reference's evaluate_one_epoch does (nerf/utils.py:1250-1252)."""
+    def eval_psnr(self, cam=0, downscale=4, use_ema=False, capture=None):
+        """use_ema: evaluate the averaged weights, as the reference's evaluate_one_epoch does (nerf/utils.py:1250-1252).  capture: the set the view
+        is taken from (default: the training capture, if there is one) -- a held-out split, for instance."""
         from .trainer import Stage0Trainer
         self.sync_parameters()
         if use_ema and self.ema is not None:
             with self.averaged_parameters():
-                return Stage0Trainer.eval_psnr(self, cam, downscale)
-        return Stage0Trainer.eval_psnr(self, cam, downscale)
+                return Stage0Trainer.eval_psnr(self, cam, downscale, capture=capture)
+        return Stage0Trainer.eval_psnr(self, cam, downscale, capture=capture)

@@ -194,7 +194,7 @@ class Stage1Engine:
             # ---- image head: loss, face errors, and d loss / d antialias output (scaled by the loss scale) in one launch
             te = (model.triangles_errors, model.triangles_errors_cnt) if opt.refine else (None, None)
             L.call("n2m_stage1_head", self.aa.data_ptr() + 12, _p(self.aa), _p(self.rast), h0, w0, int(opt.ssaa), _p(rgba_gt), _p(bg), 0.0, float(opt.lambda_rgb),
-                   float(max(opt.lambda_mask, 0.0)), _p(self.image), _p(self.depth), _p(self.ws), _p(self.trig), _p(self.loss_px), self.d_aa.data_ptr() + 12,
+                   float(tr._lambda_mask()), _p(self.image), _p(self.depth), _p(self.ws), _p(self.trig), _p(self.loss_px), self.d_aa.data_ptr() + 12,
                    _p(self.d_aa), _p(self.partial), _p(te[0]), _p(te[1]), 1, _p(self.seed), _p(self.d_rgba), s)
             # ---- backward
             self.d_clip.zero_()

@@ -47,8 +47,13 @@ class LambdaLR:
 
 
 class Stage0Trainer:
-    def __init__(self, model, opt, poses, device, rank=0, world_size=1, seed=0, ema_decay=0.95):
+    def __init__(self, model, opt, poses, device, rank=0, world_size=1, seed=0, ema_decay=0.95, capture=None):
         self.model, self.opt, self.device = model.to(device), opt, device
+        # capture (capture.Capture, opt-in): a captured image set instead of the analytic box scene, as in engine.Stage0Engine
+        self.capture = capture
+        if capture is not None:
+            capture.check_device(device)
+            poses = capture.poses
         self.poses = poses.to(device)
         # EMA of the parameters: main.py:241 (0.95 for stage 0), nerf/utils.py:544-545; one update per epoch = len(loader) steps (:1213-1214).
         # Device tensors only (the update is a HIP kernel); the CPU drivers of tests/test_parallel.py run without it.
@@ -104,6 +109,8 @@ class Stage0Trainer:
         self.boxes = synthetic.boxes(device, self.scene)
         # --enable_cam_near_far (main.py:40): every ray is clamped to its camera's sparse-point depth range (nerf/renderer.py:689-691)
         self.cam_near_far = synthetic.cam_near_far(self.poses, self.scene) if getattr(opt, "enable_cam_near_far", False) else None
+        if capture is not None:
+            self.cam_near_far = capture.cam_near_far
         self._loss_sum = torch.zeros((), device=device)
         self._loss_pending = []
         self.samples_seen = 0
@@ -127,19 +134,34 @@ class Stage0Trainer:
             self._loss_pending = []
         return self._loss_sum
 
+    def _lambda_mask(self):
+        """Weight of the mask term; 0 for a capture without an alpha channel (the reference skips the term for 3-channel images, nerf/utils.py:681)."""
+        if self.capture is not None and not self.capture.has_alpha:
+            return 0.0
+        return max(self.opt.lambda_mask, 0.0)
+
     def mark_untrained(self):
-        if self.opt.mark_untrained:
+        if self.opt.mark_untrained and self.capture is not None:
+            self.model.mark_untrained_grid(self.poses, self.capture.intrinsics, cam_near_far=self.cam_near_far)
+        elif self.opt.mark_untrained:
             f = synthetic.LEGO_FOCAL
             self.model.mark_untrained_grid(self.poses, (f, f, synthetic.LEGO_HW / 2, synthetic.LEGO_HW / 2), cam_near_far=self.cam_near_far)
 
     def batch(self):
         """(rays_o, rays_d, rgba, noises, bg) of the next batch: ONE draw of [num_rays, 6] uniforms from the ray generator, turned into
         pixels, rays, ground truth, march jitter and random background by synthetic.batch_from_uniforms."""
-        if self.images is None:
+        cap = self.capture
+        if cap is None and self.images is None:
             self.images = synthetic.preload_images(self.poses, self.boxes)     # nerf/provider.py:224-233 (`preload`)
         u = torch.rand(self.num_rays, 6, device=self.device, generator=self.gen)
-        rays_o, rays_d, rgba, nears, fars, noises, bg = synthetic.batch_from_uniforms(self.poses, self.images, u, self.model.aabb_train,
-                                                                                      self.model.min_near, cam_near_far=self.cam_near_far)
+        if cap is not None:
+            from .capture import batch_from_uniforms_u8
+            rays_o, rays_d, rgba, nears, fars, noises, bg = batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, u, self.model.aabb_train,
+                                                                                   self.model.min_near, cap.H, cap.W, cap.intrinsics,
+                                                                                   cam_near_far=self.cam_near_far)
+        else:
+            rays_o, rays_d, rgba, nears, fars, noises, bg = synthetic.batch_from_uniforms(self.poses, self.images, u, self.model.aabb_train,
+                                                                                          self.model.min_near, cam_near_far=self.cam_near_far)
         self._nears_fars = (nears, fars) if self.cam_near_far is not None else None
         return rays_o, rays_d, rgba, noises, bg
 
@@ -218,12 +240,12 @@ class Stage0Trainer:
                            nears_fars=nears_fars if ticket is None else None)
         if self.fused_loss:
             # background blend + ground-truth compositing + rgb/mask MSE + mean in one kernel (nerf/utils.py:658-683)
-            loss = photo_loss(out["image"], out["weights_sum"], images, bg_color, opt.lambda_rgb, max(opt.lambda_mask, 0.0))
+            loss = photo_loss(out["image"], out["weights_sum"], images, bg_color, opt.lambda_rgb, self._lambda_mask())
         else:
             gt_mask = images[..., 3:]
             gt_rgb = images[..., :3] * gt_mask + bg_color * (1 - gt_mask)
             loss = opt.lambda_rgb * F.mse_loss(out["image"], gt_rgb, reduction="none").mean(-1)
-            if opt.lambda_mask > 0:
+            if opt.lambda_mask > 0 and self._lambda_mask() > 0:
                 loss = loss + opt.lambda_mask * F.mse_loss(out["weights_sum"], gt_mask.squeeze(1), reduction="none")
             loss = loss.mean()
         if opt.lambda_entropy > 0:
@@ -342,21 +364,28 @@ class Stage0Trainer:
         import contextlib
         return self.ema.average_parameters() if self.ema is not None else contextlib.nullcontext()
 
-    def eval_psnr(self, cam=0, downscale=4, use_ema=False):
-        """PSNR of one rendered view against the analytic ground truth (white background).  use_ema: with the averaged weights, as the
-        reference's evaluate_one_epoch renders (nerf/utils.py:1250-1252)."""
+    def eval_psnr(self, cam=0, downscale=4, use_ema=False, capture=None):
+        """PSNR of one rendered view against the ground truth on a white background: the analytic scene, or -- trained on a capture, or handed
+        one here (a held-out split, for instance) -- view `cam` of that capture, its decoded pixels at stride `downscale` (capture.Capture.view).
+        use_ema: with the averaged weights, as the reference's evaluate_one_epoch renders (nerf/utils.py:1250-1252)."""
         if use_ema and getattr(self, "ema", None) is not None:
             with self.averaged_parameters():
-                return type(self).eval_psnr(self, cam, downscale)
+                return type(self).eval_psnr(self, cam, downscale, capture=capture)
         self.model.eval()
-        H = W = synthetic.LEGO_HW // downscale
-        dev = self.device
-        jj, ii = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
-        pix = (jj * downscale * synthetic.LEGO_HW + ii * downscale).reshape(-1)
-        rays_o, rays_d = synthetic.rays_from_pixels(self.poses, torch.full_like(pix, cam), pix)
-        rgba = synthetic.render_gt(rays_o, rays_d, self.boxes)
+        if capture is None:
+            capture = getattr(self, "capture", None)
+        if capture is not None:
+            rays_o, rays_d, rgba, _ = capture.view(cam, stride=downscale)
+            cnf = capture.cam_near_far
+        else:
+            H = W = synthetic.LEGO_HW // downscale
+            dev = self.device
+            jj, ii = torch.meshgrid(torch.arange(H, device=dev), torch.arange(W, device=dev), indexing="ij")
+            pix = (jj * downscale * synthetic.LEGO_HW + ii * downscale).reshape(-1)
+            rays_o, rays_d = synthetic.rays_from_pixels(self.poses, torch.full_like(pix, cam), pix)
+            rgba = synthetic.render_gt(rays_o, rays_d, self.boxes)
+            cnf = getattr(self, "cam_near_far", None)
         gt = rgba[:, :3] * rgba[:, 3:] + (1 - rgba[:, 3:])
-        cnf = getattr(self, "cam_near_far", None)
         out = self.model.render(rays_o, rays_d, bg_color=1, perturb=False, shading="full", dt_gamma=self.opt.dt_gamma,
                                 max_steps=self.opt.max_steps, T_thresh=1e-4, cam_near_far=None if cnf is None else cnf[cam:cam + 1])
         mse = F.mse_loss(out["image"], gt)
@@ -557,12 +586,19 @@ class Stage1Trainer:
     rasterise at ssaa x resolution, shade covered pixels with the colour networks, antialias, downscale, MSE (+ mask,
     + Laplacian smoothness, + offset L2), Adam on colour networks + vertex offsets."""
 
-    def __init__(self, model, opt, poses, vertices, triangles, device, H=synthetic.LEGO_HW, W=synthetic.LEGO_HW, rank=0, world_size=1, seed=0):
+    def __init__(self, model, opt, poses, vertices, triangles, device, H=synthetic.LEGO_HW, W=synthetic.LEGO_HW, rank=0, world_size=1, seed=0,
+                 capture=None):
         self.model, self.opt, self.device = model.to(device), opt, device
+        # capture (capture.Capture, opt-in): views, size, intrinsics and model-view-projections of a captured image set; the view cache is then
+        # filled by n2m_capture_view (rays, decoded ground truth, unit directions) instead of rays_from_pixels + render_gt
+        self.capture = capture
+        if capture is not None:
+            capture.check_device(device)
+            poses, H, W = capture.poses, capture.H, capture.W
         self.H, self.W = H, W
         self.poses = poses.to(device)
         self.views = list(range(rank, poses.shape[0], world_size))            # views shard across ranks
-        self.mvps = torch.stack([synthetic.mvp_matrix(p, H, W) for p in self.poses])
+        self.mvps = capture.mvps if capture is not None else torch.stack([synthetic.mvp_matrix(p, H, W) for p in self.poses])
         model.init_stage1(vertices, triangles)
         params = model.get_params(opt.lr) + [{"params": model.vertices_offsets, "lr": opt.lr_vert, "weight_decay": 0}]
         # main.py:221 Adam(eps=1e-15) + nerf/utils.py:506 GradScaler, as in stage 0: optim.FusedAdamAMP does both in two launches (torch:
@@ -611,6 +647,8 @@ class Stage1Trainer:
         self.fused_head = torch.device(device).type == "cuda" and int(opt.ssaa) in (1, 2)      # losses.stage1_head (False: the torch graph)
         self.packed_aa = os.environ.get("N2M_S1_PACKED_AA", "1") != "0"      # one antialias call on RGB + alpha instead of two
 
+    _lambda_mask = Stage0Trainer._lambda_mask
+
     @torch.no_grad()
     def sync_refine_state(self):
         """Views shard over the ranks, so every rank has accumulated the per-face errors of ITS views only (update_triangles_errors,
@@ -644,7 +682,7 @@ class Stage1Trainer:
         covered-pixel count, the view cache (rays / ground truth / directions do not depend on the mesh) and the background generator
         (its stream goes on, as the reference's does through a refinement) stay."""
         keep = (self.global_step, self.covered_seen, self.view_cache, self._dirs, self.gen)
-        self.__init__(self.model, self.opt, self.poses, v, f, self.device, self.H, self.W, self.rank, self.world)
+        self.__init__(self.model, self.opt, self.poses, v, f, self.device, self.H, self.W, self.rank, self.world, capture=self.capture)
         self.global_step, self.covered_seen, self.view_cache, self._dirs, self.gen = keep
 
     @torch.no_grad()
@@ -667,7 +705,12 @@ class Stage1Trainer:
         return stats
 
     def _view(self, v):
-        if v not in self.view_cache:
+        if v not in self.view_cache and self.capture is not None:
+            rays_o, rays_d, rgba, dirs = self.capture.view(v, dirs_ssaa=max(int(self.opt.ssaa), 1) if self.fused_head else 0)
+            self.view_cache[v] = (rays_o, rays_d, rgba)
+            if dirs is not None:
+                self._dirs[v] = dirs
+        elif v not in self.view_cache:
             rays_o, rays_d = synthetic.rays_from_pixels(self.poses, torch.full_like(self.pix, v), self.pix, self.H, self.W)
             self.view_cache[v] = (rays_o, rays_d, synthetic.render_gt(rays_o, rays_d, self.boxes))
         return self.view_cache[v]
@@ -707,13 +750,13 @@ class Stage1Trainer:
             if self.amp_adam:
                 seed = self.optimizer.scale if self.world == 1 else self.optimizer.scale / self.world
             loss, _, _, _, trig, loss_px = stage1_head(aa_alpha, aa_rgb, rast, rgba, bg, self.H, self.W, int(opt.ssaa), opt.lambda_rgb,
-                                                       max(opt.lambda_mask, 0.0), *te, seed=seed)
+                                                       self._lambda_mask(), *te, seed=seed)
         else:
             gt_mask = rgba[:, 3:]
             gt_rgb = rgba[:, :3] * gt_mask + bg * (1 - gt_mask)
             out = model.render_stage1(rays_o, rays_d, self.mvps[v], self.H, self.W, bg_color=bg, shading=shading)
             loss = opt.lambda_rgb * F.mse_loss(out["image"], gt_rgb, reduction="none").mean(-1)
-            if opt.lambda_mask > 0:
+            if opt.lambda_mask > 0 and self._lambda_mask() > 0:
                 loss = loss + opt.lambda_mask * F.mse_loss(out["weights_sum"].view(-1), gt_mask.view(-1), reduction="none")
             if opt.refine:
                 model.update_triangles_errors(loss.detach())

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Both stages on a captured image set in the nerf format (transforms_{train,test}.json or transforms.json + images):
+
+    tools/train_capture.py PATH --workspace DIR [--iters0 N --iters1 N --downscale k --scale s --bound b --color_space srgb|linear]
+
+  load (capture.Capture.load_nerf: the train split, and the test split if PATH has one) -> stage 0 (step executor on the uint8 bank)
+  -> export_stage0(dataset=capture, clean, decimate) -> stage 1 on that mesh (views from the capture) -> export_stage1(atlas="charts")
+  -> one JSON line: held-out PSNR of both stages (the test split; without one, the training views) and evaluate_export of the written files.
+
+Reads nothing but PATH; writes under --workspace.  With --bound > 1 stage 1 refines the inner mesh (cascade 0) only."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from nerf2mesh_amd.asset import ExportedAsset, evaluate_export, psnr
+from nerf2mesh_amd.capture import Capture
+from nerf2mesh_amd.engine import Stage0Engine
+from nerf2mesh_amd.engine_stage1 import Stage1Engine
+from nerf2mesh_amd.network import NeRFNetwork
+from nerf2mesh_amd.options import make_options
+from nerf2mesh_amd.trainer import Stage0Trainer, Stage1Trainer
+
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("path")
+ap.add_argument("--workspace", required=True)
+ap.add_argument("--iters0", type=int, default=30000)
+ap.add_argument("--iters1", type=int, default=10000)
+ap.add_argument("--downscale", type=int, default=1)
+ap.add_argument("--scale", type=float, default=0.33)
+ap.add_argument("--offset", type=float, nargs=3, default=[0, 0, 0])
+ap.add_argument("--bound", type=float, default=1)
+ap.add_argument("--color_space", choices=["srgb", "linear"], default="srgb")
+ap.add_argument("--resolution", type=int, default=None, help="marching-cubes resolution (default: the occupancy grid's)")
+ap.add_argument("--decimate_target", type=float, default=3e5)
+ap.add_argument("--texture", type=int, default=2048)
+ap.add_argument("--eval_views", type=int, default=8, help="held-out views the PSNRs are averaged over")
+ap.add_argument("--seed", type=int, default=0)
+args = ap.parse_args()
+dev = torch.device("cuda", 0)
+torch.manual_seed(args.seed)
+linear = args.color_space == "linear"
+
+
+def clock(label, t0, extra=""):
+    torch.cuda.synchronize()
+    print(f"[{label}] {time.perf_counter() - t0:8.3f} s  {extra}", flush=True)
+
+
+load = lambda split: Capture.load_nerf(args.path, split=split, scale=args.scale, offset=args.offset, downscale=args.downscale, linear=linear, device=dev)
+t0 = time.perf_counter()
+cap = load("train")
+held = load("test") if os.path.exists(os.path.join(args.path, "transforms_test.json")) else cap
+views = list(range(0, len(held), max(1, len(held) // max(1, args.eval_views))))[:args.eval_views]
+clock("load", t0, f"{len(cap)} training views {cap.H} x {cap.W} ({cap.nbytes / 1e6:.1f} MB as uint8, {'RGBA' if cap.has_alpha else 'RGB'}), "
+      f"{len(held) if held is not cap else 0} held-out views")
+
+# ---- stage 0
+opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 1 / 256, iters=args.iters0, fused_mlp=True, scale=args.scale,
+                   offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace)
+model = NeRFNetwork(opt)
+cls = Stage0Engine if Stage0Engine.supported(model, opt) else Stage0Trainer
+eng = cls(model, opt, None, dev, seed=args.seed, capture=cap)
+eng.mark_untrained()
+t0 = time.perf_counter()
+for _ in range(args.iters0):
+    eng.train_step()
+psnr0 = [eng.eval_psnr(cam=v, downscale=1, use_ema=True, capture=held) for v in views]
+clock("stage 0", t0, f"{args.iters0} steps ({cls.__name__}), held-out PSNR {np.mean(psnr0):.2f} dB")
+
+t0 = time.perf_counter()
+with eng.averaged_parameters():          # the mesh comes from the averaged weights, like the reference's (nerf/utils.py:1340-1341)
+    meshes = model.export_stage0(os.path.join(args.workspace, "mesh_stage0"), resolution=args.resolution, decimate_target=args.decimate_target,
+                                 dataset=cap, clean=True, decimate=True)
+v0, f0 = meshes[0]
+clock("export_stage0", t0, f"{v0.shape[0]} vertices, {f0.shape[0]} triangles (visibility filter, clean, decimate)")
+if f0.shape[0] == 0:
+    raise SystemExit("export_stage0 left no face: stage 0 has not found the object (more --iters0, or check --scale / --bound)")
+
+# ---- stage 1
+opt.stage, opt.iters = 1, max(args.iters1, 501)
+tr = Stage1Trainer(model, opt, None, v0, f0, dev, seed=args.seed, capture=cap)
+step = Stage1Engine(tr).train_step if Stage1Engine.supported(tr) else tr.train_step
+t0 = time.perf_counter()
+for _ in range(args.iters1):
+    step()
+model.eval()
+psnr1, eval_views = [], []
+with torch.no_grad():
+    for v in views:
+        _, rays_d, rgba, _ = held.view(v)
+        gt = rgba[:, :3] * rgba[:, 3:] + (1 - rgba[:, 3:])
+        psnr1.append(psnr(model.render_stage1(None, rays_d, held.mvps[v], held.H, held.W)["image"].view(-1, 3), gt))
+        eval_views.append((rays_d, held.mvps[v]))
+clock("stage 1", t0, f"{args.iters1} steps on {f0.shape[0]} faces, held-out PSNR {np.mean(psnr1):.2f} dB")
+
+t0 = time.perf_counter()
+out_dir = os.path.join(args.workspace, "mesh_stage1")
+model.export_stage1(out_dir, h0=args.texture, w0=args.texture, atlas="charts")
+ev = evaluate_export(model, ExportedAsset.load(out_dir), eval_views, held.H, held.W)
+clock("export_stage1", t0, "files: " + ", ".join(sorted(os.listdir(out_dir))))
+
+print(json.dumps({"train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
+                  "bank_mb": round(cap.nbytes / 1e6, 3), "iters0": args.iters0, "iters1": args.iters1, "faces": int(f0.shape[0]),
+                  "psnr_stage0": float(np.mean(psnr0)), "psnr_stage1": float(np.mean(psnr1)), "export_psnr_vs_stage1": ev["mean"],
+                  "export_psnr_per_view": ev["psnr_vs_stage1"]}))
