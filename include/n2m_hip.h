@@ -798,6 +798,15 @@ int n2m_batch_rays_u8(const float* poses, const float* uniforms, uint32_t V, uin
                       float cy, const uint32_t* bank, const float* lut, const float* aabb, float min_near, float* rays_o, float* rays_d,
                       float* rgba, float* nears, float* fars, float* noises, float* bg, int32_t* counter, const float* cam_near_far,
                       void* stream);
+/* n2m_batch_rays_u8 for the keypoints of ONE view (sparse-depth supervision, nerf/colmap_provider.py:510-522): coords [Ktot,2] i32 (row, col),
+ * kp_depth / kp_weight [Ktot] f32 are the whole CSR table of capture.Capture.sparse_depth, [first, first + K) the entries of `view`.  Ray n goes
+ * through the centre of pixel coords[first + n]; uniforms [K,6] supply the march jitter (column 2) and the background (3..5), columns 0, 1
+ * are not read.  Writes what n2m_batch_rays_u8 writes per ray (the near / far clamp is cam_near_far[view]) + gt_depth [K], depth_weight [K]. */
+int n2m_batch_rays_sparse_u8(const float* poses, const float* uniforms, uint32_t V, uint32_t view, uint32_t first, uint32_t K, uint32_t H,
+                             uint32_t W, float fx, float fy, float cx, float cy, const uint32_t* bank, const float* lut, const float* aabb,
+                             float min_near, const int32_t* coords, const float* kp_depth, const float* kp_weight, float* rays_o, float* rays_d,
+                             float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth, float* depth_weight,
+                             int32_t* counter, const float* cam_near_far, void* stream);
 /* One whole view at pixel stride `stride`: h = H / stride, w = W / stride, output pixel (y, x) = source pixel (y stride, x stride); rays_o,
  * rays_d [h*w,3], rgba [h*w,4] f32.  dirs (may be NULL): [h*ssaa * w*ssaa, 3] unit directions, every pixel's safe_normalize(d) repeated
  * ssaa x ssaa times (nearest upscale, nerf/renderer.py:821-828). */
@@ -823,7 +832,8 @@ int n2m_photo_loss_backward(const float* image, const float* weights_sum, const 
                             const float* grad_loss, float* d_image, float* d_weights_sum, void* stream);
 
 /* Training fast path: n2m_composite_rays_train_forward -> n2m_photo_loss_forward -> n2m_photo_loss_backward ->
- * n2m_composite_rays_train_backward as ONE launch (density mode, the plain rgb + mask loss: no gradient into weights or depth).
+ * n2m_composite_rays_train_backward as ONE launch (density mode, the plain rgb + mask loss: no gradient into weights or depth;
+ * n2m_composite_loss_train_ent adds the one into weights, n2m_composite_loss_train_depth the one into depth).
  * A wave composites its ray, forms the ray's loss term and gradients and runs the backward scan right away (the seed gradient
  * *grad_loss / N does not depend on the loss value).  grad_sigmas [M] / grad_rgbs [M,3] are bit-identical to the four-call chain
  * (every sample of a ray's range is written); weights_sum [N] and image [N,3] (colour before the background blend) may be NULL;
@@ -848,6 +858,17 @@ int n2m_composite_loss_train_ex(const float* sigmas, const float* rgbs, const fl
                                 float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb, float lambda_mask,
                                 const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas, float* grad_rgbs, float* partial,
                                 uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy, int alpha_mode, void* stream);
+/* n2m_composite_loss_train_ent + the sparse-depth term of nerf/utils.py:685-705 (density mode):
+ *   loss_n += lambda_depth * depth_weight[n] * (depth_n * m - gt_depth[n] * m)^2,   m = (gt_depth[n] > 0),   depth_n = sum_k w_k t_k
+ * before the mean over rays (the reference adds an [N,1] term to an [N] one; the mean of the [N,N] broadcast is that same mean).  Its derivative
+ * w.r.t. depth_n is the `grad_depth` input of composite_rays_train's backward (raymarching.cu:676-678).  depth [N] (may be NULL) <- depth_n,
+ * bit-identical to n2m_composite_rays_train_forward's; gt_depth NULL: no depth term; depth_weight NULL: 1.  With lambda_depth == 0 or
+ * gt_depth == 0 everywhere the gradients and the loss are bit-identical to n2m_composite_loss_train_ent.  alpha_mode != 0: N2M_EUNSUPPORTED. */
+int n2m_composite_loss_train_depth(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
+                                   float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb, float lambda_mask,
+                                   const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas, float* grad_rgbs, float* partial,
+                                   uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy, float* depth, const float* gt_depth,
+                                   const float* depth_weight, float lambda_depth, int alpha_mode, void* stream);
 
 /* Live-first sample order for the table backward (no reference counterpart; raymarching.cu:553,640: composite_rays_train stops a ray at
  * T < T_thresh, every later sample of the ray gets weight 0 and gradient 0 -- about half of the samples of a trained batch).

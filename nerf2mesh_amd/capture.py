@@ -16,6 +16,7 @@ camera; the reference's projection (nerf/provider.py:266-276) ignores cx, cy and
 import json
 import math
 import os
+import struct
 
 import numpy as np
 import torch
@@ -115,6 +116,258 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
     return o, d, decode_words(bank[cam, pix], lut), nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous()
 
 
+def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None):
+    """The depth-bearing batch of ONE view (nerf/colmap_provider.py:510-522): a ray through the centre of every keypoint of `view` in the
+    CSR table `sparse_depth` (SparseDepth), jitter and background from u [K_v,6] (columns 2 and 3..5).  Returns batch_from_uniforms_u8's
+    seven tensors + gt_depth [K_v], depth_weight [K_v].  On the GPU one kernel (n2m_batch_rays_sparse_u8); below it the torch statement."""
+    dev = poses.device
+    V, v = poses.shape[0], int(view)
+    first, K = sparse_depth.range(v)
+    if u.shape[0] != K:
+        raise ValueError(f"view {v} has {K} keypoints, the uniforms are for {u.shape[0]} rays")
+    fx, fy, cx, cy = (float(x) for x in intrinsics)
+    if dev.type == "cuda":
+        from . import _lib as L
+        if out is None:
+            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+            out = (f(K, 3), f(K, 3), f(K, 4), f(K), f(K), f(K), f(K, 3), f(K), f(K))
+        o, d, rgba, nears, fars, noises, bg, gtd, dw = out
+        L.call("n2m_batch_rays_sparse_u8", L.ptr(poses), L.ptr(u), V, v, first, K, H, W, fx, fy, cx, cy, L.ptr(bank), L.ptr(lut), L.ptr(aabb),
+               float(min_near), L.ptr(sparse_depth.coords), L.ptr(sparse_depth.depth), L.ptr(sparse_depth.weight), L.ptr(o), L.ptr(d), L.ptr(rgba),
+               L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(gtd), L.ptr(dw), L.ptr(counter), L.ptr(cam_near_far), L.stream())
+        return o, d, rgba, nears, fars, noises, bg, gtd, dw
+    rc = sparse_depth.coords[first:first + K].long()
+    row, col = rc[:, 0].clamp(0, H - 1), rc[:, 1].clamp(0, W - 1)
+    o, d = rays_from_pixels(poses, torch.full_like(row, v), col, row, (fx, fy, cx, cy))
+    inv = 1.0 / d
+    lo, hi = (aabb[:3] - o) * inv, (aabb[3:] - o) * inv
+    tn, tf = torch.minimum(lo, hi).amax(-1), torch.maximum(lo, hi).amin(-1)
+    miss = tn > tf
+    big = torch.finfo(torch.float32).max
+    nears = torch.where(miss, torch.full_like(tn, big), tn.clamp(min=min_near))
+    fars = torch.where(miss, torch.full_like(tf, big), tf)
+    if cam_near_far is not None:
+        nears = torch.maximum(nears, cam_near_far[v, 0])
+        fars = torch.minimum(fars, cam_near_far[v, 1])
+    if counter is not None:
+        counter.zero_()
+    return (o, d, decode_words(bank[v][row * W + col], lut), nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous(),
+            sparse_depth.depth[first:first + K].clone(), sparse_depth.weight[first:first + K].clone())
+
+
+class SparseDepth:
+    """Keypoints with a triangulated depth, per view, as a CSR table on the device (nerf/colmap_provider.py:227-278): offsets [V+1] int32,
+    coords [K,2] int32 (row, col), depth [K] fp32, weight [K] fp32.  `counts` is the host copy of the per-view sizes (a driver sizes its
+    launches from it without reading the device)."""
+
+    def __init__(self, offsets, coords, depth, weight, device="cpu"):
+        off = torch.as_tensor(offsets).to(torch.int32).cpu()
+        self.host_offsets = [int(x) for x in off]
+        self.counts = [b - a for a, b in zip(self.host_offsets[:-1], self.host_offsets[1:])]
+        K = self.host_offsets[-1]
+        self.offsets = off.to(device).contiguous()
+        self.coords = torch.as_tensor(coords).to(torch.int32).reshape(K, 2).to(device).contiguous()
+        self.depth = torch.as_tensor(depth).float().reshape(K).to(device).contiguous()
+        self.weight = torch.as_tensor(weight).float().reshape(K).to(device).contiguous()
+
+    def __len__(self):
+        return len(self.counts)
+
+    def range(self, v):
+        """(first entry, number of entries) of view v."""
+        return self.host_offsets[v], self.counts[v]
+
+    def view(self, v):
+        a, k = self.range(v)
+        return self.coords[a:a + k], self.depth[a:a + k], self.weight[a:a + k]
+
+
+class DepthSchedule:
+    """Which steps of a run are depth steps, and on which view: the reference's loader takes a depth batch when `random.random() > 0.9`
+    (nerf/colmap_provider.py:510-511) on the view its shuffled sampler hands it (:513).  Here one seeded host generator per driver draws
+    both, one decision per prepared batch, so trainer.Stage0Trainer and engine.Stage0Engine walk the same sequence however far ahead they
+    prepare.  `log` keeps the decisions (None: a plain step)."""
+
+    def __init__(self, n_views, seed=0):
+        import random
+        self.rng, self.n, self.order, self.log = random.Random(seed), int(n_views), [], []
+
+    def next(self):
+        view = None
+        if self.rng.random() > 0.9:
+            if not self.order:
+                self.order = list(range(self.n))
+                self.rng.shuffle(self.order)
+            view = self.order.pop()
+        self.log.append(view)
+        return view
+
+
+def depth_schedule_for(capture, opt, seed):
+    """The DepthSchedule of a driver, or None when the capture carries no sparse depth or opt.enable_sparse_depth is off."""
+    sd = getattr(capture, "sparse_depth", None)
+    if sd is None or not getattr(opt, "enable_sparse_depth", False):
+        return None
+    return DepthSchedule(len(sd), seed)
+
+
+# --------------------------------------------------------------------------------------------- COLMAP binary models
+# Written from COLMAP's published format description (https://colmap.github.io/format.html, "Binary File Format"; the camera model ids and
+# their parameter counts are those of src/colmap/sensor/models.h), little endian throughout:
+#   cameras.bin   u64 count; per camera: i32 id, i32 model, u64 width, u64 height, f64 params[n(model)]
+#   images.bin    u64 count; per image: i32 id, f64 q[4] (w, x, y, z), f64 t[3], i32 camera id, name (zero-terminated), u64 n2d,
+#                 n2d x (f64 x, f64 y, i64 point3D id or -1)
+#   points3D.bin  u64 count; per point: u64 id, f64 xyz[3], u8 rgb[3], f64 error, u64 track length, length x (i32 image id, i32 point2D idx)
+COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8),
+                 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4), 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
+COLMAP_DIRS = (("colmap_sparse", "0"), ("sparse", "0"), ("colmap",))
+
+
+class _Reader:
+    def __init__(self, name):
+        with open(name, "rb") as f:
+            self.buf, self.pos, self.name = f.read(), 0, name
+
+    def take(self, fmt):
+        n = struct.calcsize(fmt)
+        if self.pos + n > len(self.buf):
+            raise ValueError(f"{self.name}: truncated at byte {self.pos}")
+        out = struct.unpack_from(fmt, self.buf, self.pos)
+        self.pos += n
+        return out
+
+    def array(self, dtype, count):
+        dt = np.dtype(dtype)
+        if self.pos + dt.itemsize * count > len(self.buf):
+            raise ValueError(f"{self.name}: truncated at byte {self.pos}")
+        out = np.frombuffer(self.buf, dt, count, self.pos)
+        self.pos += dt.itemsize * count
+        return out
+
+    def cstring(self):
+        end = self.buf.find(b"\0", self.pos)
+        if end < 0:
+            raise ValueError(f"{self.name}: unterminated name at byte {self.pos}")
+        out = self.buf[self.pos:end].decode()
+        self.pos = end + 1
+        return out
+
+
+def read_colmap_cameras(name):
+    """{camera id: dict(model, width, height, params [n] f64)}."""
+    r = _Reader(name)
+    cams = {}
+    for _ in range(r.take("<Q")[0]):
+        cid, model, w, h = r.take("<iiQQ")
+        if model not in COLMAP_MODELS:
+            raise ValueError(f"{name}: unknown camera model id {model}")
+        mname, npar = COLMAP_MODELS[model]
+        cams[cid] = dict(model=mname, width=int(w), height=int(h), params=r.array("<f8", npar).copy())
+    return cams
+
+
+def read_colmap_images(name):
+    """{image id: dict(q [4] (w, x, y, z), t [3], camera_id, name, xys [n,2] f64, point3D_ids [n] i64)}."""
+    r = _Reader(name)
+    rec = np.dtype([("xy", "<f8", 2), ("id", "<i8")])
+    ims = {}
+    for _ in range(r.take("<Q")[0]):
+        iid = r.take("<i")[0]
+        qt = r.array("<f8", 7).copy()
+        cam = r.take("<i")[0]
+        fname = r.cstring()
+        p2d = r.array(rec, r.take("<Q")[0])
+        ims[iid] = dict(q=qt[:4], t=qt[4:], camera_id=cam, name=fname, xys=p2d["xy"].copy().reshape(-1, 2), point3D_ids=p2d["id"].copy())
+    return ims
+
+
+def read_colmap_points(name):
+    """(ids [M] i64 ascending, xyz [M,3] f64, error [M] f64)."""
+    r = _Reader(name)
+    ids, xyz, err = [], [], []
+    for _ in range(r.take("<Q")[0]):
+        pid, x, y, z, _r, _g, _b, e, track = r.take("<QdddBBBdQ")
+        r.array("<i4", 2 * track)
+        ids.append(pid); xyz.append((x, y, z)); err.append(e)
+    order = np.argsort(np.asarray(ids, dtype=np.int64), kind="stable")
+    return (np.asarray(ids, dtype=np.int64)[order], np.asarray(xyz, dtype=np.float64).reshape(-1, 3)[order],
+            np.asarray(err, dtype=np.float64)[order])
+
+
+def quat_to_rotmat(q):
+    """Rotation matrix of a unit quaternion (w, x, y, z)."""
+    w, x, y, z = (float(a) for a in q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]], dtype=np.float64)
+
+
+def rotmat_to_quat(R):
+    """Unit quaternion (w, x, y, z), w >= 0, of a rotation matrix (the branch with the largest pivot)."""
+    t = R[0, 0] + R[1, 1] + R[2, 2]
+    if t > 0:
+        s = math.sqrt(t + 1.0) * 2
+        q = (0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s)
+    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
+        s = math.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2]) * 2
+        q = ((R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s)
+    elif R[1, 1] > R[2, 2]:
+        s = math.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2]) * 2
+        q = ((R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s)
+    else:
+        s = math.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1]) * 2
+        q = ((R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s)
+    q = np.asarray(q, dtype=np.float64)
+    q /= np.linalg.norm(q)
+    return -q if q[0] < 0 else q
+
+
+def _rotation_between(a, b):
+    """The rotation that takes direction a to direction b (Rodrigues; nerf/colmap_provider.py:18-27 `rotmat`, whose random retry for
+    opposite directions is replaced by a fixed perpendicular axis)."""
+    a, b = a / np.linalg.norm(a), b / np.linalg.norm(b)
+    v, c = np.cross(a, b), float(np.dot(a, b))
+    if c < -1 + 1e-10:
+        axis = np.cross(a, [1.0, 0.0, 0.0] if abs(a[0]) < 0.9 else [0.0, 1.0, 0.0])
+        axis /= np.linalg.norm(axis)
+        return 2 * np.outer(axis, axis) - np.eye(3)
+    s = np.linalg.norm(v)
+    k = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
+    return np.eye(3) + k + k.dot(k) * ((1 - c) / (s ** 2 + 1e-10))
+
+
+def center_poses(poses, pts3d, enable_cam_center=False):
+    """nerf/colmap_provider.py:30-54: move the point centroid (or the camera centroid) to the origin and rotate the mean of the cameras'
+    second axis onto +z.  poses [V,4,4], pts3d [M,3], float64; returns new arrays."""
+    center = poses[:, :3, 3].mean(0) if enable_cam_center else pts3d.mean(0)
+    up = poses[:, :3, 1].mean(0)
+    R = np.eye(4)
+    R[:3, :3] = _rotation_between(up / (np.linalg.norm(up) + 1e-10), np.array([0.0, 0.0, 1.0]))
+    poses = poses.copy()
+    poses[:, :3, 3] -= center
+    return R @ poses, (pts3d - center) @ R[:3, :3].T
+
+
+def _world_flip(poses, pts):
+    """The convention change of nerf/colmap_provider.py:205-211, its own inverse on the world side: camera axes y, z negated (OpenCV ->
+    OpenGL), world (x, y, z) -> (y, x, -z) for poses and points."""
+    poses = poses.copy()
+    poses[:, :3, 1:3] *= -1
+    poses = poses[:, [1, 0, 2, 3], :]
+    poses[:, 2] *= -1
+    pts = pts[:, [1, 0, 2]].copy()
+    pts[:, 2] *= -1
+    return poses, pts
+
+
+def _read_image(name):
+    from PIL import Image
+    with Image.open(name) as im:
+        if im.mode not in ("RGB", "RGBA"):
+            im = im.convert("RGBA" if "A" in im.getbands() or "transparency" in im.info else "RGB")
+        return np.asarray(im, dtype=np.uint8)
+
+
 def box_downscale(bank, H, W, k):
     """Packed words [V,H*W] -> [V,(H//k)*(W//k)]: per-channel integer mean of every k x k block, (sum + k*k//2) // (k*k); rows and columns
     that do not fill a block are dropped.  (The reference resizes with cv2.INTER_AREA on the host; parity with its rounding is unpinned.)"""
@@ -134,6 +387,10 @@ class Capture:
     """poses [V,4,4] fp32 (camera-to-world, OpenGL: the engines' convention), H, W, intrinsics (fx, fy, cx, cy), bank [V,H*W] packed RGBA8
     (int32 storage) on `device`, has_alpha, linear (opt.color_space == 'linear'), optional cam_near_far [V,2], mvps [V,4,4].  It can be handed
     to export_stage0 as its `dataset` (.mvps, .H, .W)."""
+
+    pts_aabb = None           # [6] fp32 (host): box of the reconstruction's sparse points (load_colmap), for renderer.update_aabb
+    sparse_depth = None       # SparseDepth (load_colmap(sparse_depth=True))
+    colmap = None             # load_colmap(keep_model=True): the reconstruction's points, errors, keypoints and names, as save_colmap takes them
 
     def __init__(self, poses, bank, H, W, intrinsics, has_alpha=True, linear=False, cam_near_far=None, device=None):
         device = torch.device(device if device is not None else bank.device)
@@ -218,6 +475,135 @@ class Capture:
         cx = tr["cx"] if "cx" in tr else W / 2.0
         cy = tr["cy"] if "cy" in tr else H / 2.0
         return cls.from_arrays(np.stack(poses), np.stack(images), (fx, fy, cx, cy), linear=linear, downscale=downscale, device=device)
+
+    @classmethod
+    def load_colmap(cls, path, split="train", scale=-1, downscale=1, linear=False, enable_cam_center=False, sparse_depth=False, device="cpu",
+                    keep_model=False):
+        """A COLMAP reconstruction by the rules of nerf/colmap_provider.py:134-278, 404-435 (own reader of cameras.bin / images.bin /
+        points3D.bin, see above; looked for under colmap_sparse/0, sparse/0, colmap).  Image keys sorted, entries without a file under
+        images_{downscale}/ (else images/) dropped; poses = inv([R|t]) -> center_poses -> convention flip -> scale (-1: 1 / min |camera
+        position|); pts_aabb = box of the scaled points; per kept image the keypoints with a 3D point inside the full-resolution image give
+        cam_near_far (min, max depth) and, with sparse_depth=True, the CSR table Capture.sparse_depth.  Every 8th kept image is `val`,
+        `train` the rest, `trainval` all.  mask/NAME.png supplies alpha.  Without an images_{downscale} folder the bank's own box downscale
+        is taken (integer downscale that divides the size).  One camera model per set: kept images whose cameras differ are a ValueError.
+        keep_model=True keeps the transformed points, their errors and every kept view's keypoints on the host as Capture.colmap (what
+        save_colmap takes to write the set back); training needs none of it, so by default it is dropped."""
+        if split not in ("train", "val", "trainval"):
+            raise ValueError(f"split must be train, val or trainval, not {split!r}")
+        root = next((os.path.join(path, *c) for c in COLMAP_DIRS if os.path.exists(os.path.join(path, *c))), None)
+        if root is None:
+            raise ValueError(f"no COLMAP model under {path} (colmap_sparse/0, sparse/0, colmap)")
+        cams = read_colmap_cameras(os.path.join(root, "cameras.bin"))
+        ims = read_colmap_images(os.path.join(root, "images.bin"))
+        pids, pts3d, perr = read_colmap_points(os.path.join(root, "points3D.bin"))
+        if len(pids) == 0:
+            raise ValueError(f"{root}: the reconstruction has no 3D points")
+        ds = downscale
+        folder = os.path.join(path, f"images_{ds}")
+        own_folder = os.path.exists(folder)
+        if not own_folder:
+            folder = os.path.join(path, "images")
+        keys = [k for k in sorted(ims) if os.path.exists(os.path.join(folder, os.path.basename(ims[k]["name"])))]
+        if not keys:
+            raise FileNotFoundError(f"{root}/images.bin lists no image that exists under {folder}")
+        # one camera model per set
+        used = sorted({ims[k]["camera_id"] for k in keys})
+        intr = []
+        for c in used:
+            cam = cams[c]
+            if cam["model"] in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL"):
+                f4 = (cam["params"][0], cam["params"][0], cam["params"][1], cam["params"][2])
+            elif cam["model"] in ("PINHOLE", "OPENCV"):
+                f4 = tuple(cam["params"][:4])
+            else:
+                raise ValueError(f"unsupported COLMAP camera model: {cam['model']}")
+            intr.append((cam["height"], cam["width"]) + tuple(float(x) for x in f4))
+        if any(i != intr[0] for i in intr[1:]):
+            raise ValueError(f"the kept images use {len(used)} cameras with different parameters; a Capture holds one camera model per set "
+                             "(per-view intrinsics are not supported)")
+        h0, w0 = intr[0][:2]
+        H, W = int(round(h0 / ds)), int(round(w0 / ds))
+        fx, fy, cx, cy = (x / ds for x in intr[0][2:])
+        # poses: camera-to-world = inv([R|t]) = [R^T | -R^T t]
+        poses = np.tile(np.eye(4), (len(keys), 1, 1))
+        for n, k in enumerate(keys):
+            R = quat_to_rotmat(ims[k]["q"])
+            poses[n, :3, :3] = R.T
+            poses[n, :3, 3] = -R.T @ ims[k]["t"]
+        poses, pts = center_poses(poses, pts3d, enable_cam_center)
+        poses, pts = _world_flip(poses, pts)
+        if scale == -1:
+            scale = 1.0 / np.linalg.norm(poses[:, :3, 3], axis=-1).min()
+        poses[:, :3, 3] *= scale
+        pts = pts * scale
+        pts_aabb = np.concatenate([pts.min(0), pts.max(0)]).astype(np.float32)
+        # keypoints -> sparse depth, per kept image
+        mean_err = perr.mean()
+        cnf, tab, kps = [], [], []
+        for n, k in enumerate(keys):
+            xy, ids = ims[k]["xys"], ims[k]["point3D_ids"]
+            if keep_model:
+                found = np.searchsorted(pids, ids).clip(0, len(pids) - 1)
+                kps.append((xy, np.where((ids != -1) & (pids[found] == ids), found, -1)))       # as indices into the sorted point list
+            rowcol = np.stack([xy[:, 1], xy[:, 0]], -1)
+            m = (ids != -1) & (rowcol[:, 0] >= 0) & (rowcol[:, 0] < h0) & (rowcol[:, 1] >= 0) & (rowcol[:, 1] < w0)
+            if not m.any():
+                raise ValueError(f"image {ims[k]['name']} has no keypoint with a 3D point inside the image")
+            at = np.searchsorted(pids, ids[m])
+            if (at >= len(pids)).any() or (pids[np.minimum(at, len(pids) - 1)] != ids[m]).any():
+                raise ValueError(f"image {ims[k]['name']} refers to a 3D point that points3D.bin does not hold")
+            rc = np.round(rowcol[m] / ds).astype(np.int32)
+            rc[:, 0] = rc[:, 0].clip(0, H - 1)
+            rc[:, 1] = rc[:, 1].clip(0, W - 1)
+            P = poses[n]
+            depth = (P[:3, 3] - pts[at]) @ P[:3, 2]
+            weight = 2 * np.exp(-(perr[at] / mean_err) ** 2)
+            cnf.append([depth.min(), depth.max()])
+            tab.append((rc, depth.astype(np.float32), weight.astype(np.float32)))
+        sel = list(range(len(keys)))
+        if split == "val":
+            sel = sel[::8]
+        elif split == "train":
+            sel = [i for i in sel if i % 8 != 0]
+        if not sel:
+            raise ValueError(f"the {split} split of {len(keys)} images is empty")
+        # images (+ masks) of the split
+        mask_dir = os.path.join(path, "mask")
+        images = []
+        for i in sel:
+            base = os.path.basename(ims[keys[i]]["name"])
+            im = _read_image(os.path.join(folder, base))
+            mname = os.path.join(mask_dir, os.path.splitext(base)[0] + ".png")
+            if os.path.isdir(mask_dir) and os.path.exists(mname):
+                mk = _read_image(mname)
+                if mk.shape[:2] != im.shape[:2]:
+                    raise ValueError(f"{mname} is {mk.shape[0]} x {mk.shape[1]}, its image {im.shape[0]} x {im.shape[1]}")
+                im = np.concatenate([im[..., :3], mk[..., :1]], -1)
+            images.append(im)
+        if any(im.shape[-1] == 4 for im in images):         # a mask for some views only: the others are opaque
+            images = [im if im.shape[-1] == 4 else np.concatenate([im, np.full_like(im[..., :1], 255)], -1) for im in images]
+        if any(im.shape != images[0].shape for im in images):
+            raise ValueError("all images of a set must share one size")
+        bank, has_alpha = pack_rgba8(np.stack(images))
+        bank = bank.to(device)
+        ih, iw = images[0].shape[:2]
+        if (ih, iw) != (H, W):
+            k = int(ds)
+            if own_folder or k != ds or (ih, iw) != (h0, w0) or (ih // k, iw // k) != (H, W):
+                raise ValueError(f"the images are {ih} x {iw}, the cameras state {h0} x {w0} at downscale {ds}: only the full-size images "
+                                 "with an integer downscale that divides them can be reduced here")
+            bank = box_downscale(bank, ih, iw, k)
+        cap = cls(poses[sel].astype(np.float32), bank, H, W, (fx, fy, cx, cy), has_alpha=has_alpha, linear=linear,
+                  cam_near_far=np.asarray(cnf, dtype=np.float32)[sel], device=device)
+        cap.pts_aabb = torch.from_numpy(pts_aabb)
+        cap.scale = float(scale)
+        if keep_model:
+            cap.colmap = dict(points=pts, errors=perr, keypoints=[kps[i] for i in sel], names=[os.path.basename(ims[keys[i]]["name"]) for i in sel])
+        if sparse_depth:
+            off = np.concatenate([[0], np.cumsum([len(tab[i][1]) for i in sel])])
+            cap.sparse_depth = SparseDepth(off, np.concatenate([tab[i][0] for i in sel]), np.concatenate([tab[i][1] for i in sel]),
+                                           np.concatenate([tab[i][2] for i in sel]), device=cap.device)
+        return cap
 
     @classmethod
     def synthetic(cls, poses, scene="lego", H=synthetic.LEGO_HW, W=synthetic.LEGO_HW, intrinsics=None, alpha=True, linear=False,
@@ -309,3 +695,75 @@ class Capture:
             frames.append({"file_path": rel, "transform_matrix": m.tolist()})
         with open(os.path.join(path, f"transforms_{split}.json"), "w") as f:
             json.dump({"h": self.H, "w": self.W, "fl_x": fx, "fl_y": fy, "cx": cx, "cy": cy, "frames": frames}, f)
+
+    def save_colmap(self, path, points, errors=None, keypoints=None, names=None, scale=1.0, model="PINHOLE", folder="sparse/0"):
+        """Writes a COLMAP reconstruction (cameras.bin, images.bin, points3D.bin under `folder`, images/NAME.png) such that
+        load_colmap(path, "trainval", scale=scale) of an already centred set (one that load_colmap produced, saved with the points, errors,
+        keypoints and names of its Capture.colmap) gives this set back; any other set comes back re-centred by center_poses.  Mirrors
+        save_nerf.  points [M,3] in this set's world (numbered from 1 in the file), errors [M] (default 1), keypoints: per view (xy [n,2] in
+        pixels, index [n] into `points` or -1) -- default: every point projected into every view it lies in front of and inside of.  One
+        camera (id 1) of `model` PINHOLE or SIMPLE_PINHOLE (needs fx = fy) at the stored size."""
+        from PIL import Image
+        points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        M, V = len(points), len(self)
+        ids = np.arange(1, M + 1, dtype=np.int64)
+        errors = np.ones(M) if errors is None else np.asarray(errors, dtype=np.float64).reshape(M)
+        names = [f"r_{v}.png" for v in range(V)] if names is None else list(names)
+        fx, fy, cx, cy = self.intrinsics
+        if model == "PINHOLE":
+            mid, params = 1, (fx, fy, cx, cy)
+        elif model == "SIMPLE_PINHOLE" and fx == fy:
+            mid, params = 0, (fx, cx, cy)
+        else:
+            raise ValueError("save_colmap writes PINHOLE, or SIMPLE_PINHOLE when fx == fy")
+        # back to COLMAP's frame: undo the scale, then the convention change (its own inverse on the world side)
+        poses = self.poses.double().cpu().numpy().copy()
+        poses[:, :3, 3] /= scale
+        poses = poses[:, [1, 0, 2, 3], :]              # inverse of _world_flip: the world side is its own inverse, then the camera axes
+        poses[:, 2] *= -1
+        poses[:, :3, 1:3] *= -1
+        pw = points / scale
+        pw = pw[:, [1, 0, 2]].copy()
+        pw[:, 2] *= -1
+        if keypoints is None:
+            keypoints = []
+            for v in range(V):
+                pc = (pw - poses[v, :3, 3]) @ poses[v, :3, :3]          # camera coordinates (x right, y down, z forward)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    x, y = fx * pc[:, 0] / pc[:, 2] + cx, fy * pc[:, 1] / pc[:, 2] + cy
+                m = (pc[:, 2] > 0) & (x >= 0) & (x < self.W) & (y >= 0) & (y < self.H)
+                keypoints.append((np.stack([x[m], y[m]], -1), np.nonzero(m)[0]))
+        root = os.path.join(path, *folder.split("/"))
+        os.makedirs(root, exist_ok=True)
+        os.makedirs(os.path.join(path, "images"), exist_ok=True)
+        with open(os.path.join(root, "cameras.bin"), "wb") as f:
+            f.write(struct.pack("<Q", 1))
+            f.write(struct.pack("<iiQQ", 1, mid, self.W, self.H))
+            f.write(np.asarray(params, dtype="<f8").tobytes())
+        by = self.bank_bytes().cpu().numpy()
+        tracks = {}
+        with open(os.path.join(root, "images.bin"), "wb") as f:
+            f.write(struct.pack("<Q", V))
+            for v in range(V):
+                Rt = poses[v, :3, :3].T                                  # world-to-camera rotation
+                f.write(struct.pack("<i", v + 1))
+                f.write(np.concatenate([rotmat_to_quat(Rt), -Rt @ poses[v, :3, 3]]).astype("<f8").tobytes())
+                f.write(struct.pack("<i", 1))
+                f.write(names[v].encode() + b"\0")
+                xy, idx = keypoints[v]
+                xy, idx = np.asarray(xy, dtype=np.float64).reshape(-1, 2), np.asarray(idx, dtype=np.int64).reshape(-1)
+                pid = np.where(idx >= 0, ids[np.clip(idx, 0, M - 1)], -1)
+                rec = np.empty(len(idx), dtype=np.dtype([("xy", "<f8", 2), ("id", "<i8")]))
+                rec["xy"], rec["id"] = xy, pid
+                f.write(struct.pack("<Q", len(idx)))
+                f.write(rec.tobytes())
+                for j, p in enumerate(pid):
+                    if p != -1:
+                        tracks.setdefault(int(p), []).append((v + 1, j))
+                Image.fromarray(by[v] if self.has_alpha else np.ascontiguousarray(by[v, :, :, :3])).save(os.path.join(path, "images", names[v]))
+        with open(os.path.join(root, "points3D.bin"), "wb") as f:
+            f.write(struct.pack("<Q", M))
+            for m in range(M):
+                tr = tracks.get(int(ids[m]), [])
+                f.write(struct.pack("<QdddBBBdQ", int(ids[m]), *pw[m], 128, 128, 128, float(errors[m]), len(tr)))
+                f.write(np.asarray(tr, dtype="<i4").tobytes())

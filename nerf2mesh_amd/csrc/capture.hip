@@ -48,6 +48,49 @@ batch_rays_u8_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* _
     if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
 }
 
+// batch_rays_u8_kernel for the keypoints of ONE view (sparse-depth supervision, nerf/colmap_provider.py:510-522): ray n goes through the
+// centre of pixel coords[n] = (row, col) of that view instead of a pixel drawn from the uniforms; jitter and background still come from
+// uniforms [K,6] (columns 2 and 3..5; columns 0, 1 are not read).  Also copies the keypoints' depth and weight into the batch.
+__global__ void __launch_bounds__(256)
+batch_rays_sparse_u8_kernel(const float* __restrict__ P /*[4,4] of the view*/, const float* __restrict__ u /*[K,6]*/, uint32_t K, uint32_t H,
+                            uint32_t W, float fx, float fy, float cx, float cy, const uint32_t* __restrict__ bank /*[H W] of the view*/,
+                            const float* __restrict__ lut /*[2,256]*/, const float* __restrict__ aabb, float min_near,
+                            const int32_t* __restrict__ coords /*[K,2]*/, const float* __restrict__ kp_depth /*[K]*/,
+                            const float* __restrict__ kp_weight /*[K]*/, float* __restrict__ rays_o, float* __restrict__ rays_d,
+                            float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ noises,
+                            float* __restrict__ bg, float* __restrict__ gt_depth, float* __restrict__ depth_weight,
+                            int32_t* __restrict__ counter, const float* __restrict__ near_far /*[2] of the view or NULL*/) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0 && counter) counter[0] = 0;
+    if (n >= K) return;
+    const float* __restrict__ un = u + (size_t)n * 6;
+    // (row, col) clamped to the image: the loader clips them already, the clamp keeps a hand-made table inside the bank
+    const uint32_t row = (uint32_t)min(max(coords[(size_t)n * 2], 0), (int32_t)H - 1);
+    const uint32_t col = (uint32_t)min(max(coords[(size_t)n * 2 + 1], 0), (int32_t)W - 1);
+    const float i = (float)col + 0.5f, j = (float)row + 0.5f;
+    const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
+    float o[3], d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
+        o[k] = P[4 * k + 3];
+        rays_d[(size_t)n * 3 + k] = d[k];
+        rays_o[(size_t)n * 3 + k] = o[k];
+    }
+    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = decode_rgba8(bank[(size_t)row * W + (size_t)col], lut);
+    float tn, tf;
+    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
+    if (near_far) {
+        tn = fmaxf(tn, near_far[0]);
+        tf = fminf(tf, near_far[1]);
+    }
+    nears[n] = tn; fars[n] = tf;
+    noises[n] = un[2];
+    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
+    gt_depth[n] = kp_depth[n];
+    depth_weight[n] = kp_weight[n];
+}
+
 // One whole view at pixel stride s: output pixel (y, x) of the h x w grid is source pixel (y s, x s), its ray goes through that pixel's
 // centre.  dirs (optional): safe_normalize(d) (nerf/utils.py) of every pixel repeated ssaa x ssaa times, i.e. the nearest upscale to
 // [h ssaa, w ssaa] the stage-1 renderer shades with (nerf/renderer.py:821-828).
@@ -116,6 +159,26 @@ extern "C" int n2m_batch_rays_u8(const float* poses, const float* uniforms, uint
     batch_rays_u8_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W, fx, fy, cx, cy, bank, lut, aabb,
                                                                                 min_near, rays_o, rays_d, rgba, nears, fars, noises, bg, counter,
                                                                                 cam_near_far);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
+
+// The keypoints [first, first + K) of the sparse-depth table belong to `view`; coords / kp_depth / kp_weight are the WHOLE table's arrays.
+extern "C" int n2m_batch_rays_sparse_u8(const float* poses, const float* uniforms, uint32_t V, uint32_t view, uint32_t first, uint32_t K, uint32_t H,
+                                        uint32_t W, float fx, float fy, float cx, float cy, const uint32_t* bank, const float* lut, const float* aabb,
+                                        float min_near, const int32_t* coords, const float* kp_depth, const float* kp_weight, float* rays_o,
+                                        float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth,
+                                        float* depth_weight, int32_t* counter, const float* cam_near_far, void* stream) {
+    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(bank); N2M_NOTNULL(lut); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o); N2M_NOTNULL(rays_d);
+    N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises); N2M_NOTNULL(coords); N2M_NOTNULL(kp_depth); N2M_NOTNULL(kp_weight);
+    N2M_NOTNULL(gt_depth); N2M_NOTNULL(depth_weight);
+    N2M_REQUIRE(view < V && H >= 1 && W >= 1 && (uint64_t)H * W < (1ull << 24) && (uint64_t)first + K < (1ull << 31), N2M_EINVAL,
+                "batch_rays_sparse_u8: need view < V, 1 <= H*W < 2^24 and first + K < 2^31");
+    if (K == 0) return 0;
+    batch_rays_sparse_u8_kernel<<<n2m_ceil_div(K, 256), 256, 0, (hipStream_t)stream>>>(
+        poses + (size_t)view * 16, uniforms, K, H, W, fx, fy, cx, cy, bank + (size_t)view * H * W, lut, aabb, min_near, coords + (size_t)first * 2,
+        kp_depth + first, kp_weight + first, rays_o, rays_d, rgba, nears, fars, noises, bg, gt_depth, depth_weight, counter,
+        cam_near_far ? cam_near_far + (size_t)view * 2 : nullptr);
     N2M_CHECK_LAUNCH();
     return 0;
 }

@@ -1076,7 +1076,18 @@ __device__ __forceinline__ float n2m_entropy_grad(float x) {       // d H(clamp(
     return (x >= lo && x <= hi) ? (-log2f(x) - 1.4426950408889634f) + (log2f(1.0f - x) + 1.4426950408889634f) : 0.0f;
 }
 // ALPHA: the SDF recipe's alpha mode (raymarching.cu:534,671: alpha = the `sigmas` input itself, backward scale 1 / (1 - alpha))
-template <bool ENT, bool ALPHA = false>
+// DEPTH: + the sparse-depth term of nerf/utils.py:685-705, lambda_depth * depth_weight_n * (depth_n m - gt_depth_n m)^2 with m = (gt_depth_n > 0)
+// and depth_n = sum_k w_k t_k.  The reference adds this [N,1] term to the [N] per-ray loss and takes the mean of the [N,N] broadcast, which is
+// mean_n(loss_n) + lambda_depth * mean_n(term_n): the same mean over rays taken here.  The term's derivative w.r.t. depth_n enters the backward
+// where the reference kernel reads grad_depth[n] (raymarching.cu:676-678: g_depth * (T t - (d_final - d_run))).  The non-DEPTH instantiations
+// do not read the argument block and compile to the code they had before.
+struct CompositeDepthArgs {
+    float* depth;                  // [N] out (may be NULL)
+    const float* gt_depth;         // [N] (NULL: no depth term)
+    const float* depth_weight;     // [N] (NULL: 1)
+    float lambda_depth;
+};
+template <bool ENT, bool ALPHA = false, bool DEPTH = false>
 __global__ void __launch_bounds__(1024)
 composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ ts,
                             const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float T_thresh, const float* __restrict__ gt,
@@ -1084,7 +1095,7 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                             const float* __restrict__ grad_loss, float* __restrict__ weights_sum, float* __restrict__ image,
                             float* __restrict__ grad_sigmas, float* __restrict__ grad_rgbs, float* __restrict__ partial,
                             uint32_t* __restrict__ ticket, float* __restrict__ loss, float* __restrict__ loss_sum, float lambda_entropy,
-                            int32_t* __restrict__ live_out, uint32_t* __restrict__ block_live_out) {
+                            int32_t* __restrict__ live_out, uint32_t* __restrict__ block_live_out, CompositeDepthArgs dargs) {
     __shared__ float wave_loss[16];
     __shared__ uint32_t wave_live[16];
     __shared__ bool last_block;
@@ -1102,9 +1113,14 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
         float bgv[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) bgv[c] = bg ? bg[(size_t)n * 3 + c] : bg_scalar;
+        float gtd = 0.f, dwt = 1.f;        // DEPTH: the ray's keypoint depth (0: none) and weight
+        if (DEPTH && dargs.gt_depth) {
+            gtd = dargs.gt_depth[n];
+            if (dargs.depth_weight) dwt = dargs.depth_weight[n];
+        }
         // ---- forward
-        float rF = 0, gF = 0, bF = 0, wsF = 0;
-        float a0 = 0.f, dt0 = 0.f, cr0 = 0.f, cg0 = 0.f, cb0 = 0.f;     // the first 64 samples stay in registers for the backward pass
+        float rF = 0, gF = 0, bF = 0, wsF = 0, dF = 0;
+        float a0 = 0.f, dt0 = 0.f, cr0 = 0.f, cg0 = 0.f, cb0 = 0.f, tm0 = 0.f;     // the first 64 samples stay in registers for the backward pass
         float entF = 0.f;                  // ENT: sum of H(clamp(w)) over this ray's samples (weights after the early stop are zeros)
         uint32_t visited = 0;
         if (whole) {
@@ -1114,12 +1130,13 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                 const uint32_t k = base + lane;
                 const bool valid = k < cnt;
                 const size_t i = (size_t)off + k;
-                float alpha = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
+                float alpha = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, tmid = 0.f;
                 if (valid) {
                     const float2 tt = *reinterpret_cast<const float2*>(ts + 2 * i);
                     alpha = ALPHA ? sigmas[i] : 1.0f - expf(-sigmas[i] * tt.y);
                     cr = rgbs[3 * i]; cg = rgbs[3 * i + 1]; cb = rgbs[3 * i + 2];
                     if (base == 0) { a0 = alpha; dt0 = tt.y; cr0 = cr; cg0 = cg; cb0 = cb; }
+                    if (DEPTH) { tmid = tt.x; if (base == 0) tm0 = tmid; }
                 }
                 const float incl = n2m_wave_scan_mul(1.0f - alpha, lane);
                 const float excl = n2m_lane_below(incl, 1.0f);
@@ -1128,6 +1145,7 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                 const int last = stop ? (int)__ffsll((long long)stop) - 1 : 63;
                 const float w = (valid && lane <= last) ? alpha * T_before : 0.f;
                 rF += w * cr; gF += w * cg; bF += w * cb; wsF += w;
+                if (DEPTH) dF += w * tmid;          // composite_train_fwd_kernel's depth: per-lane sums over the chunks, then the wave sum
                 if (ENT) {
                     if (valid) entF += n2m_entropy(fminf(fmaxf(w, 1e-5f), 1.0f - 1e-5f));
                     visited = min(cnt, base + 64u);
@@ -1136,6 +1154,7 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                 carry_T = n2m_lane63(T_after);
             }
             rF = n2m_wave_sum(rF); gF = n2m_wave_sum(gF); bF = n2m_wave_sum(bF); wsF = n2m_wave_sum(wsF);
+            if (DEPTH) dF = n2m_wave_sum(dF);
             if (ENT) entF = n2m_wave_sum(entF) + (float)(cnt - visited) * n2m_entropy(1e-5f);
         } else if (ENT && cnt != 0 && off < M) entF = (float)(M - off) * n2m_entropy(1e-5f);      // cut off by M: its weights stay zero
         // ---- loss term of the ray and its gradients (wave-uniform)
@@ -1163,6 +1182,15 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
             gws += gscale * lambda_entropy * n2m_entropy_grad(wsF);
             gE = gl * lambda_entropy * inv_m;
         }
+        float gd = 0.f;                     // DEPTH: d loss / d depth_n, the grad_depth[n] of composite_rays_train's backward
+        if (DEPTH) {
+            if (gtd > 0.0f) {               // m = 1 (m = 0: both products are zeros, the term and its gradient vanish)
+                const float ed = dF - gtd;
+                l_ray += dargs.lambda_depth * (dwt * (ed * ed));
+                gd = gscale * dargs.lambda_depth * (dwt * (2.0f * ed));
+            }
+            if (lane == 0 && dargs.depth) dargs.depth[n] = dF;
+        }
         if (lane == 0) {
             if (weights_sum) weights_sum[n] = wsF;
             if (image) { image[3 * n] = rF; image[3 * n + 1] = gF; image[3 * n + 2] = bF; }
@@ -1175,7 +1203,7 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                 grad_rgbs[3 * (size_t)i] = 0.f; grad_rgbs[3 * (size_t)i + 1] = 0.f; grad_rgbs[3 * (size_t)i + 2] = 0.f;
             }
         } else if (whole) {
-            float carry_T = 1.0f, r0 = 0, g0 = 0, b0 = 0, ws0 = 0;
+            float carry_T = 1.0f, r0 = 0, g0 = 0, b0 = 0, ws0 = 0, d0 = 0;
             bool stopped = false;
             for (uint32_t base = 0; base < cnt; base += 64) {
                 const uint32_t k = base + lane;
@@ -1185,12 +1213,13 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                     if (valid) { grad_sigmas[i] = 0.f; grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f; }
                     continue;
                 }
-                float alpha = 0.f, dt = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
-                if (base == 0) { alpha = a0; dt = dt0; cr = cr0; cg = cg0; cb = cb0; }      // the forward pass's own values (zeros where !valid)
+                float alpha = 0.f, dt = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, tmid = 0.f;
+                if (base == 0) { alpha = a0; dt = dt0; cr = cr0; cg = cg0; cb = cb0; tmid = tm0; }      // the forward pass's own values (zeros where !valid)
                 else if (valid) {
                     const float2 tt = *reinterpret_cast<const float2*>(ts + 2 * i);
                     alpha = ALPHA ? sigmas[i] : 1.0f - expf(-sigmas[i] * tt.y);
                     dt = tt.y;
+                    if (DEPTH) tmid = tt.x;
                     cr = rgbs[3 * i]; cg = rgbs[3 * i + 1]; cb = rgbs[3 * i + 2];
                 }
                 const float incl = n2m_wave_scan_mul(1.0f - alpha, lane);
@@ -1204,19 +1233,24 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                 const float g = g0 + n2m_wave_scan_add(w * cg, lane);
                 const float b = b0 + n2m_wave_scan_add(w * cb, lane);
                 const float ws = ws0 + n2m_wave_scan_add(w, lane);
+                float d = 0.f;
+                if (DEPTH) d = d0 + n2m_wave_scan_add(w * tmid, lane);        // wave-uniform branch: every lane takes the scan
                 if (live) {
                     grad_rgbs[3 * i] = gi[0] * w; grad_rgbs[3 * i + 1] = gi[1] * w; grad_rgbs[3 * i + 2] = gi[2] * w;
-                    // composite_train_bwd_kernel's expression with grad_weights = grad_depth = 0 (their terms are exact zeros there)
+                    // composite_train_bwd_kernel's expression with grad_weights = grad_depth = 0 (their terms are exact zeros there);
+                    // DEPTH: its grad_depth term, and the same + 0 as before for a ray without one (gd == 0), so those rays keep their bits
                     const float gw = ENT ? gE * n2m_entropy_grad(w) : 0.f;      // grad_weights[i]
                     const float gscl = ALPHA ? 1.0f / (1.0f - alpha) : dt;      // (alpha = 1: inf, un-guarded like the reference; the caller clips alpha)
                     grad_sigmas[i] = gscl * (gi[0] * (T_after * cr - (rF - r)) + gi[1] * (T_after * cg - (gF - g)) +
-                                           gi[2] * (T_after * cb - (bF - b)) + (gws + gw) * (T_after - (wsF - ws)) + 0.f * 0.f);
+                                           gi[2] * (T_after * cb - (bF - b)) + (gws + gw) * (T_after - (wsF - ws)) +
+                                           ((DEPTH && gd != 0.f) ? gd * (T_after * tmid - (dF - d)) : 0.f * 0.f));
                 } else if (valid) {
                     grad_sigmas[i] = 0.f; grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f;
                 }
                 if (stop) { stopped = true; continue; }
                 carry_T = n2m_lane63(T_after);
                 r0 = n2m_lane63(r); g0 = n2m_lane63(g); b0 = n2m_lane63(b); ws0 = n2m_lane63(ws);
+                if (DEPTH) d0 = n2m_lane63(d);
             }
         }
     }
@@ -1759,15 +1793,15 @@ extern "C" int n2m_composite_loss_train_ex(const float* sigmas, const float* rgb
         N2M_REQUIRE(lambda_entropy <= 0.0f, N2M_EUNSUPPORTED, "composite_loss_train: alpha mode with the entropy term is not built");
         N2M_LAUNCH((composite_loss_train_kernel<false, true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar,
                                                                                      lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas,
-                                                                                     grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, g_live_out, g_block_live_out);
+                                                                                     grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, g_live_out, g_block_live_out, CompositeDepthArgs{});
     } else if (lambda_entropy > 0.0f)
         N2M_LAUNCH((composite_loss_train_kernel<true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar,
                                                                               lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas,
-                                                                              grad_rgbs, partial, ticket, loss, loss_sum, lambda_entropy, g_live_out, g_block_live_out);
+                                                                              grad_rgbs, partial, ticket, loss, loss_sum, lambda_entropy, g_live_out, g_block_live_out, CompositeDepthArgs{});
     else
         N2M_LAUNCH((composite_loss_train_kernel<false>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar,
                                                                                lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas,
-                                                                               grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, g_live_out, g_block_live_out);
+                                                                               grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, g_live_out, g_block_live_out, CompositeDepthArgs{});
     N2M_CHECK_LAUNCH();
     return 0;
 }
@@ -1787,6 +1821,33 @@ extern "C" int n2m_composite_loss_train(const float* sigmas, const float* rgbs, 
                                         float* grad_rgbs, float* partial, uint32_t* ticket, float* loss, float* loss_sum, void* stream) {
     return n2m_composite_loss_train_ent(sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar, lambda_rgb, lambda_mask, grad_loss,
                                         weights_sum, image, grad_sigmas, grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, stream);
+}
+
+// ... + the sparse-depth term (DEPTH instantiations of the same kernel; density mode only)
+extern "C" int n2m_composite_loss_train_depth(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
+                                              float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb,
+                                              float lambda_mask, const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas,
+                                              float* grad_rgbs, float* partial, uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy,
+                                              float* depth, const float* gt_depth, const float* depth_weight, float lambda_depth, int alpha_mode,
+                                              void* stream) {
+    N2M_REQUIRE(!alpha_mode, N2M_EUNSUPPORTED, "composite_loss_train_depth: the depth term is built for density mode only");
+    N2M_NOTNULL(rays); N2M_NOTNULL(gt_rgba); N2M_NOTNULL(grad_loss); N2M_NOTNULL(partial);
+    N2M_REQUIRE(ticket == nullptr || loss != nullptr, N2M_ENULL, "composite_loss_train: a ticket needs the loss output");
+    if (M > 0) { N2M_NOTNULL(sigmas); N2M_NOTNULL(rgbs); N2M_NOTNULL(ts); N2M_NOTNULL(grad_sigmas); N2M_NOTNULL(grad_rgbs); }
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    N2M_PROF_K(N2M_K_COMPOSITE_FWD, s, 28.0 * M + 28.0 * N + 44.0 * M + 48.0 * N + 12.0 * N);   // + gt_depth, depth_weight read, depth stored
+    const CompositeDepthArgs da{depth, gt_depth, depth_weight, lambda_depth};
+    if (lambda_entropy > 0.0f)
+        N2M_LAUNCH((composite_loss_train_kernel<true, false, true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg,
+                   bg_scalar, lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas, grad_rgbs, partial, ticket, loss, loss_sum,
+                   lambda_entropy, g_live_out, g_block_live_out, da);
+    else
+        N2M_LAUNCH((composite_loss_train_kernel<false, false, true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg,
+                   bg_scalar, lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas, grad_rgbs, partial, ticket, loss, loss_sum, 0.0f,
+                   g_live_out, g_block_live_out, da);
+    N2M_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int n2m_composite_rays_train_backward(const float* grad_weights, const float* grad_weights_sum,

@@ -62,6 +62,8 @@ class _RayBufs:
         f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         self.o, self.d, self.rgba = f(cap, 3), f(cap, 3), f(cap, 4)
         self.nears, self.fars, self.noises, self.bg_buf = f(cap), f(cap), f(cap), f(cap, 3)
+        self.gtd, self.dw = f(cap), f(cap)      # keypoint depth and weight of a depth batch (capture.batch_sparse_u8)
+        self.depth_view = None                  # the view of a depth batch, None for a plain one
         self.u = self.bg = None
         self.rays = torch.empty(cap, 2, dtype=torch.int32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -121,6 +123,12 @@ class Stage0Engine:
         self.cam_near_far = synthetic.cam_near_far(self.poses, self.scene) if getattr(opt, "enable_cam_near_far", False) else None
         if capture is not None:
             self.cam_near_far = capture.cam_near_far
+        # --enable_sparse_depth: one batch in ten is all keypoints of one view (capture.DepthSchedule, the same sequence as Stage0Trainer's); the
+        # ray buffers are sized for the largest view from the start
+        from .capture import depth_schedule_for
+        self.depth_schedule = depth_schedule_for(capture, opt, seed + rank)
+        self._depth_rays = 0 if self.depth_schedule is None else int(max(capture.sparse_depth.counts))
+        self._min_rays = max(8192, self._depth_rays)
         self.samples_seen = self.rays_seen = 0
         self.last_num_points = 0
         self._loss_pending, self._loss_sum = [], torch.zeros(1, device=dev)
@@ -313,7 +321,8 @@ class Stage0Engine:
         return (bool(getattr(opt, "fused_mlp", False)) and bool(opt.fp16) and getattr(opt, "ind_dim", 0) == 0
                 and _affine(float(model.bound)) is not None and same_geometry(e1, e2) and e1.embeddings.shape[1] == 1
                 and e2.embeddings.shape[1] == 2 and (sdf or not getattr(opt, "progressive_level", False))
-                and opt.patch_size == 1 and (sdf or model.max_level >= e1.num_levels) and not (sdf and opt.lambda_entropy > 0))
+                and opt.patch_size == 1 and (sdf or model.max_level >= e1.num_levels) and not (sdf and opt.lambda_entropy > 0)
+                and not (sdf and getattr(opt, "enable_sparse_depth", False)))      # the depth term is built for density mode
 
     @property
     def loss_acc(self):
@@ -337,7 +346,7 @@ class Stage0Engine:
         self._cur = (self._cur + 1) % len(self._bufs)
         b = self._bufs[self._cur]
         if b is None or b.cap < N:
-            b = self._bufs[self._cur] = _RayBufs(max(int(N * 1.5), 8192), self.device)
+            b = self._bufs[self._cur] = _RayBufs(max(int(N * 1.5), self._min_rays), self.device)
         return b
 
     def _sample_bufs(self, b, cap_m):
@@ -352,7 +361,8 @@ class Stage0Engine:
         """Step-local buffers, grow-only (level-major feature layouts are [16, M] with the step's own M as the stride)."""
         cm, cn = self._work_cap
         if M > cm or N > cn:
-            cm, cn = max(cm, int(M * 1.25) + 1024), max(cn, int(N * 1.5) + 1024)
+            # (the ray part never starts below the largest depth batch: no regrowth of the step's workspace at the first depth step)
+            cm, cn = max(cm, int(M * 1.25) + 1024), max(cn, int(N * 1.5) + 1024, self._depth_rays)
             dev = self.device
             f = lambda n: torch.empty(n, dtype=torch.float32, device=dev)
             w = self._w = {}
@@ -385,8 +395,8 @@ class Stage0Engine:
             self.sync_parameters(density_only=True)      # the refresh evaluates the density from the fp32 table: gather the other ranks' rows
         self.model.update_extra_state()
 
-    def _prepare(self, N):
-        """Batch of N rays: pixel choice, rays + ground truth, near/far, march pass 1 (count + offset scan), count on its way to the host.
+    def _prepare(self, N, depth_view=None):
+        """Batch of N rays (depth_view: a depth batch, its N rays go through the keypoints of that view -- n2m_batch_rays_sparse_u8): pixel choice, rays + ground truth, near/far, march pass 1 (count + offset scan), count on its way to the host.
         Reads the cameras, the images and the occupancy bit field only."""
         opt, model, dev = self.opt, self.model, self.device
         cap = self.capture
@@ -399,7 +409,12 @@ class Stage0Engine:
         b.u = torch.rand(N, 6, device=dev, generator=self.gen)
         self._aabb = model.aabb_train
         b.bg = b.bg_buf if opt.background != "white" else None
-        if cap is not None:
+        b.depth_view = depth_view
+        if depth_view is not None:
+            from .capture import batch_sparse_u8
+            batch_sparse_u8(self.poses, cap.bank, cap.lut, b.u, depth_view, cap.sparse_depth, self._aabb, model.min_near, cap.H, cap.W, cap.intrinsics,
+                            out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg, b.gtd, b.dw), counter=b.counter, cam_near_far=self.cam_near_far)
+        elif cap is not None:
             from .capture import batch_from_uniforms_u8
             batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, b.u, self._aabb, model.min_near, cap.H, cap.W, cap.intrinsics,
                                    out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg), counter=b.counter, cam_near_far=self.cam_near_far)
@@ -467,14 +482,17 @@ class Stage0Engine:
             prev = self._last                           # batch j-1 (still queued, or the one the running step consumes)
             if prev is not None:                        # N(j) from M(j-1)
                 M = self._count(prev)
-                if opt.adaptive_num_rays and M > 0:
+                if opt.adaptive_num_rays and M > 0 and prev.depth_view is None:      # (a depth batch does not steer the ray count)
                     self.num_rays = max(1, int(round((opt.num_points / M) * prev.N)))
             N = int(self.num_rays)
+            view = self.depth_schedule.next() if self.depth_schedule is not None else None
+            if view is not None:
+                N = self.capture.sparse_depth.counts[view]
             defer = False
             if need_refresh or not self.overlap or self._marker is None:
                 if need_refresh:
                     self._refresh()
-                b = self._prepare(N)
+                b = self._prepare(N, view)
                 if need_refresh and self.overlap and self._marker is not None:
                     # the batch behind this one needs THIS batch's count, which the host can only wait for -- and the running step cannot be
                     # enqueued before it has that count either.  So the next batch is prepared right behind the step's first launch (the
@@ -488,7 +506,7 @@ class Stage0Engine:
                 after_refresh = (j - 2) % opt.update_extra_interval == 0 and getattr(self, "_post_refresh", None) is not None
                 self.side.wait_event(self._post_refresh if after_refresh else self._marker)
                 with torch.cuda.stream(self.side):
-                    b = self._prepare(N)
+                    b = self._prepare(N, view)
                 main = torch.cuda.current_stream(self.device)
                 b.u.record_stream(main)
             b.index = j
@@ -961,8 +979,13 @@ class Stage0Engine:
         if order:
             L.call("n2m_composite_live_counts", _p(w["live"]), _p(w["block_live"]))
         try:
-            L.call("n2m_composite_loss_train_ent", _p(w["sigma"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb, lam_mask,
-                   _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, float(max(opt.lambda_entropy, 0.0)), s)      # loss value: summed by the scaler kernel
+            if b.depth_view is not None:      # depth step (nerf/utils.py:685-705): the same head + the keypoints' depth term
+                L.call("n2m_composite_loss_train_depth", _p(w["sigma"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb,
+                       lam_mask, _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, float(max(opt.lambda_entropy, 0.0)),
+                       None, _p(b.gtd), _p(b.dw), float(opt.lambda_depth * min(1.0, self.global_step / 1000)), 0, s)
+            else:
+                L.call("n2m_composite_loss_train_ent", _p(w["sigma"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb, lam_mask,
+                       _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, float(max(opt.lambda_entropy, 0.0)), s)      # loss value: summed by the scaler kernel
         finally:
             if order:
                 L.call("n2m_composite_live_counts", None, None)

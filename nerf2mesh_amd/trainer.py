@@ -111,6 +111,10 @@ class Stage0Trainer:
         self.cam_near_far = synthetic.cam_near_far(self.poses, self.scene) if getattr(opt, "enable_cam_near_far", False) else None
         if capture is not None:
             self.cam_near_far = capture.cam_near_far
+        # --enable_sparse_depth (nerf/colmap_provider.py:510-522, nerf/utils.py:685-705): one step in ten takes all keypoints of one view
+        from .capture import depth_schedule_for
+        self.depth_schedule = depth_schedule_for(capture, opt, seed + rank)
+        self._depth = None            # (gt_depth, depth_weight) of the batch batch() made last, None for a plain batch
         self._loss_sum = torch.zeros((), device=device)
         self._loss_pending = []
         self.samples_seen = 0
@@ -153,6 +157,17 @@ class Stage0Trainer:
         cap = self.capture
         if cap is None and self.images is None:
             self.images = synthetic.preload_images(self.poses, self.boxes)     # nerf/provider.py:224-233 (`preload`)
+        view = self.depth_schedule.next() if self.depth_schedule is not None else None
+        self._depth = None
+        if view is not None:
+            from .capture import batch_sparse_u8
+            u = torch.rand(cap.sparse_depth.counts[view], 6, device=self.device, generator=self.gen)
+            rays_o, rays_d, rgba, nears, fars, noises, bg, gtd, dw = batch_sparse_u8(self.poses, cap.bank, cap.lut, u, view, cap.sparse_depth,
+                                                                                     self.model.aabb_train, self.model.min_near, cap.H, cap.W,
+                                                                                     cap.intrinsics, cam_near_far=self.cam_near_far)
+            self._depth = (gtd, dw)
+            self._nears_fars = (nears, fars) if self.cam_near_far is not None else None
+            return rays_o, rays_d, rgba, noises, bg
         u = torch.rand(self.num_rays, 6, device=self.device, generator=self.gen)
         if cap is not None:
             from .capture import batch_from_uniforms_u8
@@ -193,7 +208,7 @@ class Stage0Trainer:
         with torch.cuda.stream(side):
             nxt = self._prepare()
         rays_o, rays_d, images, ticket, bg, noises = nxt
-        for t in (rays_o, rays_d, images, bg, noises, ticket.rays, ticket.counter, ticket.noises) + tuple(ticket.keep) + tuple(ticket.spec or ()):
+        for t in (self._depth or ()) + (rays_o, rays_d, images, bg, noises, ticket.rays, ticket.counter, ticket.noises) + tuple(ticket.keep) + tuple(ticket.spec or ()):
             if torch.is_tensor(t):
                 t.record_stream(main)          # allocated on the side stream, consumed on the main one
         return nxt
@@ -206,6 +221,7 @@ class Stage0Trainer:
             self._next = self._prepare()
         rays_o, rays_d, images, ticket, bg_color, noises = self._next
         nears_fars = self._nears_fars                      # of THIS batch (batch() sets it; the overlapped preparation below replaces it)
+        depth_gt = self._depth                             # likewise: (gt_depth, depth_weight) of a depth step, else None
         self._next = None
         self.global_step += 1
         self.optimizer.zero_grad(set_to_none=True)
@@ -229,7 +245,7 @@ class Stage0Trainer:
             ticket = raymarching.march_rays_train_finish(ticket)
             M0 = ticket[0].shape[0]
             self.last_num_points = M0
-            if opt.adaptive_num_rays and M0 > 0:                             # nerf/utils.py:796-797
+            if opt.adaptive_num_rays and M0 > 0 and depth_gt is None:        # nerf/utils.py:796-797 (a depth step does not steer the ray count)
                 self.num_rays = max(1, int(round((opt.num_points / M0) * self.num_rays)))
             adapted = True
             self._next = self._prepare_overlapped()
@@ -248,6 +264,10 @@ class Stage0Trainer:
             if opt.lambda_mask > 0 and self._lambda_mask() > 0:
                 loss = loss + opt.lambda_mask * F.mse_loss(out["weights_sum"], gt_mask.squeeze(1), reduction="none")
             loss = loss.mean()
+        if depth_gt is not None:
+            # nerf/utils.py:685-705; the reference adds this [N,1] term to the [N] loss and means the [N,N] broadcast, which is this mean
+            from .losses import sparse_depth_loss
+            loss = loss + opt.lambda_depth * min(1.0, self.global_step / 1000) * sparse_depth_loss(out["depth"], *depth_gt)
         if opt.lambda_entropy > 0:
             w = out["weights"].clamp(1e-5, 1 - 1e-5)
             w2 = out["weights_sum"].clamp(1e-5, 1 - 1e-5)
@@ -262,7 +282,7 @@ class Stage0Trainer:
         self.last_num_points = M
         self.samples_seen += M
         self.rays_seen += N
-        if opt.adaptive_num_rays and M > 0 and not adapted:              # nerf/utils.py:796-797
+        if opt.adaptive_num_rays and M > 0 and not adapted and depth_gt is None:              # nerf/utils.py:796-797
             self.num_rays = max(1, int(round((opt.num_points / M) * self.num_rays)))
 
         # TV regulariser (nerf/utils.py:812-821 adds it to the unscaled gradients after backward).  Fast path: hand it to the

@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
-"""Both stages on a captured image set in the nerf format (transforms_{train,test}.json or transforms.json + images):
+"""Both stages on a captured image set in the nerf format (transforms_{train,test}.json or transforms.json + images) or, with
+--data_format colmap, on a COLMAP reconstruction (colmap_sparse/0 | sparse/0 | colmap + images[_k]/; capture.Capture.load_colmap):
 
     tools/train_capture.py PATH --workspace DIR [--iters0 N --iters1 N --downscale k --scale s --bound b --color_space srgb|linear]
+                           [--data_format colmap [--enable_sparse_depth --lambda_depth w] [--enable_cam_near_far] [--enable_cam_center]]
+
+  colmap: --scale defaults to -1 (1 / the nearest camera's distance), the model's training box is the sparse points' (update_aabb,
+  main.py:234-235), --enable_cam_near_far clamps every ray to its view's keypoint depth range, --enable_sparse_depth makes one step in
+  ten a depth step, and the held-out views are the `val` split (every 8th image).
 
   load (capture.Capture.load_nerf: the train split, and the test split if PATH has one) -> stage 0 (step executor on the uint8 bank)
   -> export_stage0(dataset=capture, clean, decimate) -> stage 1 on that mesh (views from the capture) -> export_stage1(atlas="charts")
@@ -32,7 +38,12 @@ ap.add_argument("--workspace", required=True)
 ap.add_argument("--iters0", type=int, default=30000)
 ap.add_argument("--iters1", type=int, default=10000)
 ap.add_argument("--downscale", type=int, default=1)
-ap.add_argument("--scale", type=float, default=0.33)
+ap.add_argument("--scale", type=float, default=None, help="default: 0.33 (nerf), -1 = automatic (colmap)")
+ap.add_argument("--data_format", choices=["nerf", "colmap"], default="nerf")
+ap.add_argument("--enable_sparse_depth", action="store_true")
+ap.add_argument("--enable_cam_near_far", action="store_true")
+ap.add_argument("--enable_cam_center", action="store_true")
+ap.add_argument("--lambda_depth", type=float, default=0.1)
 ap.add_argument("--offset", type=float, nargs=3, default=[0, 0, 0])
 ap.add_argument("--bound", type=float, default=1)
 ap.add_argument("--color_space", choices=["srgb", "linear"], default="srgb")
@@ -45,6 +56,11 @@ args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(args.seed)
 linear = args.color_space == "linear"
+colmap = args.data_format == "colmap"
+if args.scale is None:
+    args.scale = -1 if colmap else 0.33
+if not colmap and (args.enable_sparse_depth or args.enable_cam_near_far or args.enable_cam_center):
+    ap.error("--enable_sparse_depth / --enable_cam_near_far / --enable_cam_center need --data_format colmap (the sparse points supply them)")
 
 
 def clock(label, t0, extra=""):
@@ -52,18 +68,35 @@ def clock(label, t0, extra=""):
     print(f"[{label}] {time.perf_counter() - t0:8.3f} s  {extra}", flush=True)
 
 
-load = lambda split: Capture.load_nerf(args.path, split=split, scale=args.scale, offset=args.offset, downscale=args.downscale, linear=linear, device=dev)
+def load(split):
+    if not colmap:
+        return Capture.load_nerf(args.path, split=split, scale=args.scale, offset=args.offset, downscale=args.downscale, linear=linear, device=dev)
+    c = Capture.load_colmap(args.path, split=split, scale=args.scale, downscale=args.downscale, linear=linear,
+                            enable_cam_center=args.enable_cam_center, sparse_depth=args.enable_sparse_depth and split == "train", device=dev)
+    if not args.enable_cam_near_far:
+        c.cam_near_far = None
+    return c
+
+
 t0 = time.perf_counter()
 cap = load("train")
-held = load("test") if os.path.exists(os.path.join(args.path, "transforms_test.json")) else cap
+if colmap:
+    held = load("val")
+else:
+    held = load("test") if os.path.exists(os.path.join(args.path, "transforms_test.json")) else cap
 views = list(range(0, len(held), max(1, len(held) // max(1, args.eval_views))))[:args.eval_views]
 clock("load", t0, f"{len(cap)} training views {cap.H} x {cap.W} ({cap.nbytes / 1e6:.1f} MB as uint8, {'RGBA' if cap.has_alpha else 'RGB'}), "
       f"{len(held) if held is not cap else 0} held-out views")
 
 # ---- stage 0
 opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 1 / 256, iters=args.iters0, fused_mlp=True, scale=args.scale,
-                   offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace)
+                   offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace,
+                   data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_cam_near_far=args.enable_cam_near_far,
+                   lambda_depth=args.lambda_depth)
 model = NeRFNetwork(opt)
+if colmap:
+    model.to(dev)
+    model.update_aabb(cap.pts_aabb.to(dev))              # main.py:234-235
 cls = Stage0Engine if Stage0Engine.supported(model, opt) else Stage0Trainer
 eng = cls(model, opt, None, dev, seed=args.seed, capture=cap)
 eng.mark_untrained()
@@ -105,7 +138,8 @@ model.export_stage1(out_dir, h0=args.texture, w0=args.texture, atlas="charts")
 ev = evaluate_export(model, ExportedAsset.load(out_dir), eval_views, held.H, held.W)
 clock("export_stage1", t0, "files: " + ", ".join(sorted(os.listdir(out_dir))))
 
-print(json.dumps({"train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
+depth_steps = sum(v is not None for v in eng.depth_schedule.log[:args.iters0]) if getattr(eng, "depth_schedule", None) is not None else 0
+print(json.dumps({"data_format": args.data_format, "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
                   "bank_mb": round(cap.nbytes / 1e6, 3), "iters0": args.iters0, "iters1": args.iters1, "faces": int(f0.shape[0]),
                   "psnr_stage0": float(np.mean(psnr0)), "psnr_stage1": float(np.mean(psnr1)), "export_psnr_vs_stage1": ev["mean"],
                   "export_psnr_per_view": ev["psnr_vs_stage1"]}))
