@@ -807,6 +807,19 @@ int n2m_batch_rays_sparse_u8(const float* poses, const float* uniforms, uint32_t
                              float min_near, const int32_t* coords, const float* kp_depth, const float* kp_weight, float* rays_o, float* rays_d,
                              float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth, float* depth_weight,
                              int32_t* counter, const float* cam_near_far, void* stream);
+/* n2m_batch_rays_u8 + the dense-depth target of --enable_dense_depth (nerf/colmap_provider.py:552-553): depth_bank [V, H*W] f32
+ * (capture.Capture.dense_depth), gt_depth [N] f32 <- depth_bank[view_n, pixel_n], one 4-byte gather at the index the colour word is read
+ * from.  Every other output has n2m_batch_rays_u8's bits.  depth_bank or gt_depth NULL: N2M_ENULL. */
+int n2m_batch_rays_u8_depth(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
+                            float cx, float cy, const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb,
+                            float min_near, float* rays_o, float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg,
+                            float* gt_depth, int32_t* counter, const float* cam_near_far, void* stream);
+/* One view of the dense-depth bank: dst [H*W] f32 = bilinear(src [h,w] f32) * scale + bias.  cv2.INTER_LINEAR's geometry: source
+ * coordinate (x + 0.5) * rx - 0.5 and (y + 0.5) * ry - 0.5 with rx = w / W, ry = h / H rounded to fp32 by the caller, both taps of an axis
+ * clamped to the edge, fp32 weights, a + (b - a) * t per axis (columns, then rows), multiply and add unfused: bit for bit
+ * capture.dense_depth_fill on CPU tensors.  h == H, w == W: dst = src * scale + bias.  1 <= h, w < 2^24, H*W < 2^32. */
+int n2m_depth_bank_fill(const float* src, uint32_t h, uint32_t w, uint32_t H, uint32_t W, float ry, float rx, float scale, float bias,
+                        float* dst, void* stream);
 /* One whole view at pixel stride `stride`: h = H / stride, w = W / stride, output pixel (y, x) = source pixel (y stride, x stride); rays_o,
  * rays_d [h*w,3], rgba [h*w,4] f32.  dirs (may be NULL): [h*ssaa * w*ssaa, 3] unit directions, every pixel's safe_normalize(d) repeated
  * ssaa x ssaa times (nearest upscale, nerf/renderer.py:821-828). */

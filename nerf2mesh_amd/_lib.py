@@ -140,6 +140,9 @@ SIGNATURES = {
     "n2m_batch_rays_u8": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_batch_rays_sparse_u8": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_batch_rays_u8_depth": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp],
+    "n2m_depth_bank_fill": [_vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
     "n2m_capture_view": [_vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "n2m_capture_box_downscale": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_adam_step": [_vp, ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp],

@@ -83,12 +83,26 @@ def decode_words(words, lut):
     return torch.cat([lut[0][b[:, :3]], lut[1][b[:, 3:]]], -1).view(*words.shape, 4)
 
 
-def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None):
+def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None, dense_depth=None):
     """synthetic.batch_from_uniforms with the ground truth gathered from a packed uint8 bank [V,H*W] and decoded through `lut`.  On the GPU
-    one kernel (n2m_batch_rays_u8); below it the torch statement of the same arithmetic, taken on the CPU."""
+    one kernel (n2m_batch_rays_u8); below it the torch statement of the same arithmetic, taken on the CPU.  dense_depth [V,H*W] fp32
+    (Capture.dense_depth, --enable_dense_depth): an eighth tensor gt_depth [N] = dense_depth[view_n, pixel_n] follows the seven (`out`
+    then has eight entries); on the GPU n2m_batch_rays_u8_depth."""
     dev = poses.device
     N, V = u.shape[0], poses.shape[0]
     fx, fy, cx, cy = (float(x) for x in intrinsics)
+    if dense_depth is not None and tuple(dense_depth.shape) != tuple(bank.shape):
+        raise ValueError(f"the depth bank is {tuple(dense_depth.shape)}, the image bank {tuple(bank.shape)}")
+    if dev.type == "cuda" and dense_depth is not None:
+        from . import _lib as L
+        if out is None:
+            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+            out = (f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3), f(N))
+        o, d, rgba, nears, fars, noises, bg, gtd = out
+        L.call("n2m_batch_rays_u8_depth", L.ptr(poses), L.ptr(u), V, N, H, W, fx, fy, cx, cy, L.ptr(bank), L.ptr(dense_depth), L.ptr(lut), L.ptr(aabb),
+               float(min_near), L.ptr(o), L.ptr(d), L.ptr(rgba), L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(gtd), L.ptr(counter),
+               L.ptr(cam_near_far), L.stream())
+        return o, d, rgba, nears, fars, noises, bg, gtd
     if dev.type == "cuda":
         from . import _lib as L
         if out is None:
@@ -113,7 +127,8 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
         fars = torch.minimum(fars, cam_near_far[cam, 1])
     if counter is not None:
         counter.zero_()
-    return o, d, decode_words(bank[cam, pix], lut), nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous()
+    seven = (o, d, decode_words(bank[cam, pix], lut), nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous())
+    return seven if dense_depth is None else seven + (dense_depth[cam, pix],)
 
 
 def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None):
@@ -153,6 +168,78 @@ def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, 
         counter.zero_()
     return (o, d, decode_words(bank[v][row * W + col], lut), nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous(),
             sparse_depth.depth[first:first + K].clone(), sparse_depth.weight[first:first + K].clone())
+
+
+def resize_linear_at(src, H, W, rows, cols):
+    """src [h,w] fp32 resized to [H,W] and read at output pixels (rows, cols) (int tensors): cv2.INTER_LINEAR's geometry -- source coordinate
+    (x + 0.5) * (w / W) - 0.5 per axis (the ratio rounded to fp32 once), the two taps of an axis clamped to the edge, fp32 weights,
+    a + (b - a) * t per axis (columns, then rows), so a pixel between two equal taps -- every pixel at h == H, w == W -- has their value
+    exactly.  Torch statement of n2m_depth_bank_fill: every operation below is one fp32 rounding in the kernel's operand order."""
+    h, w = src.shape
+    ry, rx = (torch.tensor(float(np.float32(a / b)), dtype=torch.float32, device=src.device) for a, b in ((h, H), (w, W)))
+    sy, sx = (rows.float() + 0.5) * ry - 0.5, (cols.float() + 0.5) * rx - 0.5
+    fy0, fx0 = sy.floor(), sx.floor()
+    ty, tx = sy - fy0, sx - fx0
+    y0, y1 = fy0.long().clamp(0, h - 1), (fy0.long() + 1).clamp(0, h - 1)
+    x0, x1 = fx0.long().clamp(0, w - 1), (fx0.long() + 1).clamp(0, w - 1)
+    a, b, c, e = src[y0, x0], src[y0, x1], src[y1, x0], src[y1, x1]
+    top, bot = a + (b - a) * tx, c + (e - c) * tx
+    return top + (bot - top) * ty
+
+
+def dense_depth_fill(src, H, W, scale=1.0, bias=0.0, out=None):
+    """One row of the dense-depth bank: src [h,w] fp32 -> [H*W] fp32 = resize_linear_at(every pixel) * scale + bias (scale, bias rounded to
+    fp32; multiply, then add).  On the GPU one kernel (n2m_depth_bank_fill) writing `out`; below it the torch statement, taken on the CPU."""
+    if src.dim() != 2 or src.dtype != torch.float32:
+        raise ValueError("a depth map must be a 2-D fp32 tensor")
+    h, w = src.shape
+    if src.is_cuda:
+        from . import _lib as L
+        src = src.contiguous()
+        if out is None:
+            out = torch.empty(H * W, dtype=torch.float32, device=src.device)
+        L.call("n2m_depth_bank_fill", L.ptr(src), h, w, int(H), int(W), float(np.float32(h / H)), float(np.float32(w / W)), float(scale), float(bias),
+               L.ptr(out), L.stream())
+        return out
+    jj, ii = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    s32, b32 = torch.tensor(float(scale), dtype=torch.float32), torch.tensor(float(bias), dtype=torch.float32)
+    val = resize_linear_at(src.contiguous(), H, W, jj.reshape(-1), ii.reshape(-1)) * s32 + b32
+    if out is not None:
+        out.copy_(val)
+        return out
+    return val
+
+
+def fit_scale_bias(x, y, w):
+    """(scale, bias) that map a dense depth map onto a view's sparse depths: x [K] the map at the keypoints, y [K] their triangulated depth,
+    w [K] their weight (nerf/colmap_provider.py:298-321).  The reference fits with sklearn's RANSACRegressor, whose random draws cannot be
+    reproduced; here the deterministic weighted least squares, float64, in closed form from the five sums -- no random consensus: an
+    outlier is down-weighted by its reprojection error, not rejected.  The reference's two fall-backs follow as written: a negative scale
+    -> the line through the two most confident samples; still negative -> y0 / x0 with bias 0.  Fewer than two samples, all x equal or no
+    weight at all go straight to the fall-backs (a two-sample line with x0 == x1 counts as failed)."""
+    x, y, w = (np.asarray(a, dtype=np.float64).reshape(-1) for a in (x, y, w))
+    if len(x) == 0:
+        raise ValueError("no keypoint to calibrate the depth map with")
+    scale, bias = -1.0, 0.0
+    if len(x) >= 2 and x.min() != x.max():
+        sw, swx, swy, swxx, swxy = w.sum(), (w * x).sum(), (w * y).sum(), (w * x * x).sum(), (w * x * y).sum()
+        det = sw * swxx - swx * swx
+        if sw > 0 and det > 0:
+            scale = (sw * swxy - swx * swy) / det
+            bias = (swy - scale * swx) / sw
+    if scale < 0:
+        order = np.argsort(w, kind="stable")[::-1]
+        x0, y0 = x[order[0]], y[order[0]]
+        scale = -1.0
+        if len(x) >= 2 and x[order[1]] != x0:
+            x1, y1 = x[order[1]], y[order[1]]
+            scale = (y0 - y1) / (x0 - x1)
+            bias = y0 - x0 * scale
+        if scale < 0:
+            if x0 == 0:
+                raise ValueError("the depth map is 0 at the most confident keypoint: no scale can be taken from it")
+            scale, bias = y0 / x0, 0.0
+    return float(scale), float(bias)
 
 
 class SparseDepth:
@@ -209,6 +296,20 @@ def depth_schedule_for(capture, opt, seed):
     if sd is None or not getattr(opt, "enable_sparse_depth", False):
         return None
     return DepthSchedule(len(sd), seed)
+
+
+def dense_depth_for(capture, opt):
+    """The depth bank a driver gathers from on every step, or None with opt.enable_dense_depth off.  The option needs a capture that holds
+    a bank, and excludes opt.enable_sparse_depth: the reference builds only one of the two (nerf/colmap_provider.py:333-337)."""
+    if not getattr(opt, "enable_dense_depth", False):
+        return None
+    if capture is None:
+        raise ValueError("enable_dense_depth needs a capture (Capture.load_colmap(..., dense_depth=True)): the synthetic scene has no depth maps")
+    if getattr(capture, "dense_depth", None) is None:
+        raise ValueError("enable_dense_depth is set, but the capture holds no dense-depth bank: load it with Capture.load_colmap(..., dense_depth=True)")
+    if getattr(opt, "enable_sparse_depth", False):
+        raise ValueError("enable_dense_depth and enable_sparse_depth exclude each other: a step has one depth target")
+    return capture.dense_depth
 
 
 # --------------------------------------------------------------------------------------------- COLMAP binary models
@@ -390,6 +491,9 @@ class Capture:
 
     pts_aabb = None           # [6] fp32 (host): box of the reconstruction's sparse points (load_colmap), for renderer.update_aabb
     sparse_depth = None       # SparseDepth (load_colmap(sparse_depth=True))
+    dense_depth = None        # [V,H*W] fp32 on the device (load_colmap(dense_depth=True)): depths/NAME.npy resized and calibrated per view
+    dense_depth_scale_bias = None     # [V,2] float64 (host): the (scale, bias) fitted per view
+    dense_depth_samples = None        # keep_model=True: per view [K,3] float64 (host), what was fitted: map at the keypoints, their depth, weight
     colmap = None             # load_colmap(keep_model=True): the reconstruction's points, errors, keypoints and names, as save_colmap takes them
 
     def __init__(self, poses, bank, H, W, intrinsics, has_alpha=True, linear=False, cam_near_far=None, device=None):
@@ -478,7 +582,7 @@ class Capture:
 
     @classmethod
     def load_colmap(cls, path, split="train", scale=-1, downscale=1, linear=False, enable_cam_center=False, sparse_depth=False, device="cpu",
-                    keep_model=False):
+                    keep_model=False, dense_depth=False):
         """A COLMAP reconstruction by the rules of nerf/colmap_provider.py:134-278, 404-435 (own reader of cameras.bin / images.bin /
         points3D.bin, see above; looked for under colmap_sparse/0, sparse/0, colmap).  Image keys sorted, entries without a file under
         images_{downscale}/ (else images/) dropped; poses = inv([R|t]) -> center_poses -> convention flip -> scale (-1: 1 / min |camera
@@ -487,7 +591,10 @@ class Capture:
         `train` the rest, `trainval` all.  mask/NAME.png supplies alpha.  Without an images_{downscale} folder the bank's own box downscale
         is taken (integer downscale that divides the size).  One camera model per set: kept images whose cameras differ are a ValueError.
         keep_model=True keeps the transformed points, their errors and every kept view's keypoints on the host as Capture.colmap (what
-        save_colmap takes to write the set back); training needs none of it, so by default it is dropped."""
+        save_colmap takes to write the set back); training needs none of it, so by default it is dropped.
+        dense_depth=True (--enable_dense_depth, :281-327): every view of the split needs depths/<stem of its name>.npy, a 2-D float array of
+        any size; it is resized to [H,W] (resize_linear_at), calibrated to the view's keypoints by one (scale, bias) (fit_scale_bias, a
+        deterministic weighted least squares in the place of the reference's RANSAC) and stored as a row of Capture.dense_depth."""
         if split not in ("train", "val", "trainval"):
             raise ValueError(f"split must be train, val or trainval, not {split!r}")
         root = next((os.path.join(path, *c) for c in COLMAP_DIRS if os.path.exists(os.path.join(path, *c))), None)
@@ -559,7 +666,7 @@ class Capture:
             depth = (P[:3, 3] - pts[at]) @ P[:3, 2]
             weight = 2 * np.exp(-(perr[at] / mean_err) ** 2)
             cnf.append([depth.min(), depth.max()])
-            tab.append((rc, depth.astype(np.float32), weight.astype(np.float32)))
+            tab.append((rc, depth.astype(np.float32), weight.astype(np.float32), depth, weight))
         sel = list(range(len(keys)))
         if split == "val":
             sel = sel[::8]
@@ -567,6 +674,11 @@ class Capture:
             sel = [i for i in sel if i % 8 != 0]
         if not sel:
             raise ValueError(f"the {split} split of {len(keys)} images is empty")
+        depth_files = [os.path.join(path, "depths", os.path.splitext(os.path.basename(ims[keys[i]]["name"]))[0] + ".npy") for i in sel]
+        if dense_depth:
+            for name in depth_files:
+                if not os.path.exists(name):
+                    raise FileNotFoundError(f"dense depth asked for, but there is no {name}")
         # images (+ masks) of the split
         mask_dir = os.path.join(path, "mask")
         images = []
@@ -603,6 +715,26 @@ class Capture:
             off = np.concatenate([[0], np.cumsum([len(tab[i][1]) for i in sel])])
             cap.sparse_depth = SparseDepth(off, np.concatenate([tab[i][0] for i in sel]), np.concatenate([tab[i][1] for i in sel]),
                                            np.concatenate([tab[i][2] for i in sel]), device=cap.device)
+        if dense_depth:
+            cap.dense_depth = torch.empty(len(sel), H * W, dtype=torch.float32, device=cap.device)
+            cap.dense_depth_scale_bias = np.zeros((len(sel), 2), dtype=np.float64)
+            samples = []
+            for n, i in enumerate(sel):
+                m = np.load(depth_files[n])
+                if m.ndim != 2 or m.size == 0 or not np.issubdtype(m.dtype, np.number):
+                    raise ValueError(f"{depth_files[n]} holds an array of shape {m.shape}, not a 2-D depth map")
+                m = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32))
+                rc = torch.from_numpy(tab[i][0]).long()
+                x = resize_linear_at(m, H, W, rc[:, 0], rc[:, 1]).double().numpy()        # the resized map at the keypoints, on the host
+                try:
+                    sb = fit_scale_bias(x, tab[i][3], tab[i][4])
+                except ValueError as e:
+                    raise ValueError(f"{depth_files[n]}: {e}") from None
+                cap.dense_depth_scale_bias[n] = sb
+                samples.append(np.stack([x, tab[i][3], tab[i][4]], -1))
+                dense_depth_fill(m.to(cap.device), H, W, sb[0], sb[1], out=cap.dense_depth[n])      # one view at a time: no full-size host copy
+            if keep_model:
+                cap.dense_depth_samples = samples
         return cap
 
     @classmethod
@@ -640,7 +772,7 @@ class Capture:
 
     @property
     def nbytes(self):
-        return self.bank.numel() * 4
+        return self.bank.numel() * 4 + (0 if self.dense_depth is None else self.dense_depth.numel() * 4)
 
     def bank_bytes(self):
         """uint8 view [V,H,W,4] of the bank (R, G, B, A)."""
@@ -696,13 +828,15 @@ class Capture:
         with open(os.path.join(path, f"transforms_{split}.json"), "w") as f:
             json.dump({"h": self.H, "w": self.W, "fl_x": fx, "fl_y": fy, "cx": cx, "cy": cy, "frames": frames}, f)
 
-    def save_colmap(self, path, points, errors=None, keypoints=None, names=None, scale=1.0, model="PINHOLE", folder="sparse/0"):
+    def save_colmap(self, path, points, errors=None, keypoints=None, names=None, scale=1.0, model="PINHOLE", folder="sparse/0",
+                    depths=None):
         """Writes a COLMAP reconstruction (cameras.bin, images.bin, points3D.bin under `folder`, images/NAME.png) such that
         load_colmap(path, "trainval", scale=scale) of an already centred set (one that load_colmap produced, saved with the points, errors,
         keypoints and names of its Capture.colmap) gives this set back; any other set comes back re-centred by center_poses.  Mirrors
         save_nerf.  points [M,3] in this set's world (numbered from 1 in the file), errors [M] (default 1), keypoints: per view (xy [n,2] in
         pixels, index [n] into `points` or -1) -- default: every point projected into every view it lies in front of and inside of.  One
-        camera (id 1) of `model` PINHOLE or SIMPLE_PINHOLE (needs fx = fy) at the stored size."""
+        camera (id 1) of `model` PINHOLE or SIMPLE_PINHOLE (needs fx = fy) at the stored size.  depths: one 2-D array per view, of any
+        size, written as depths/<stem of the view's name>.npy (what load_colmap(dense_depth=True) reads)."""
         from PIL import Image
         points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
         M, V = len(points), len(self)
@@ -761,6 +895,12 @@ class Capture:
                     if p != -1:
                         tracks.setdefault(int(p), []).append((v + 1, j))
                 Image.fromarray(by[v] if self.has_alpha else np.ascontiguousarray(by[v, :, :, :3])).save(os.path.join(path, "images", names[v]))
+        if depths is not None:
+            if len(depths) != V or any(np.ndim(d) != 2 for d in depths):
+                raise ValueError(f"depths must be one 2-D array per view ({V} views)")
+            os.makedirs(os.path.join(path, "depths"), exist_ok=True)
+            for v in range(V):
+                np.save(os.path.join(path, "depths", os.path.splitext(names[v])[0] + ".npy"), np.asarray(depths[v]))
         with open(os.path.join(root, "points3D.bin"), "wb") as f:
             f.write(struct.pack("<Q", M))
             for m in range(M):

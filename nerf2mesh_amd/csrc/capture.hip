@@ -91,6 +91,67 @@ batch_rays_sparse_u8_kernel(const float* __restrict__ P /*[4,4] of the view*/, c
     depth_weight[n] = kp_weight[n];
 }
 
+// batch_rays_u8_kernel + the dense-depth target of --enable_dense_depth (nerf/colmap_provider.py:552-553): gt_depth[n] is gathered from the
+// fp32 depth bank [V,HW] at the index the colour word is read from.  Everything else is batch_rays_u8_kernel operand for operand.
+__global__ void __launch_bounds__(256)
+batch_rays_u8_depth_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, uint32_t W,
+                           uint32_t HW, float fx, float fy, float cx, float cy, const uint32_t* __restrict__ bank /*[V,HW]*/,
+                           const float* __restrict__ depth_bank /*[V,HW]*/, const float* __restrict__ lut /*[2,256]*/,
+                           const float* __restrict__ aabb, float min_near, float* __restrict__ rays_o, float* __restrict__ rays_d,
+                           float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ noises,
+                           float* __restrict__ bg, float* __restrict__ gt_depth, int32_t* __restrict__ counter,
+                           const float* __restrict__ cam_near_far /*[V,2] or NULL*/) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0 && counter) counter[0] = 0;
+    if (n >= N) return;
+    const float* __restrict__ un = u + (size_t)n * 6;
+    const uint32_t v = min(V - 1u, (uint32_t)(un[0] * (float)V)), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
+    const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
+    const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
+    const float* __restrict__ P = poses + (size_t)v * 16;
+    float o[3], d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
+        o[k] = P[4 * k + 3];
+        rays_d[(size_t)n * 3 + k] = d[k];
+        rays_o[(size_t)n * 3 + k] = o[k];
+    }
+    const size_t at = (size_t)v * HW + (size_t)p;
+    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = decode_rgba8(bank[at], lut);
+    gt_depth[n] = depth_bank[at];
+    float tn, tf;
+    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
+    if (cam_near_far) {
+        tn = fmaxf(tn, cam_near_far[2 * v]);
+        tf = fminf(tf, cam_near_far[2 * v + 1]);
+    }
+    nears[n] = tn; fars[n] = tf;
+    noises[n] = un[2];
+    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
+}
+
+// One view of the dense-depth bank (capture.dense_depth_fill): dst [H,W] = bilinear(src [h,w]) * scale + bias with cv2.INTER_LINEAR's
+// geometry -- source coordinate (x + 0.5) * rx - 0.5 per axis (rx = w / W, ry = h / H as the host rounded them to fp32), the two taps of
+// an axis clamped to the edge, fp32 weights, a + (b - a) * t per axis (columns first), so equal taps give their value exactly.  A thread
+// per output pixel; the operand order is the torch statement's and the file is compiled without contraction: bit for bit.
+__global__ void __launch_bounds__(256)
+depth_bank_fill_kernel(const float* __restrict__ src /*[h,w]*/, uint32_t h, uint32_t w, uint32_t H, uint32_t W, float ry, float rx, float scale,
+                       float bias, float* __restrict__ dst /*[H,W]*/) {
+    const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= (size_t)H * W) return;
+    const uint32_t y = (uint32_t)(n / W), x = (uint32_t)(n % W);
+    const float sx = ((float)x + 0.5f) * rx - 0.5f, sy = ((float)y + 0.5f) * ry - 0.5f;
+    const float fx0 = floorf(sx), fy0 = floorf(sy);
+    const float tx = sx - fx0, ty = sy - fy0;
+    const int32_t ix = (int32_t)fx0, iy = (int32_t)fy0;
+    const size_t x0 = (size_t)min(max(ix, 0), (int32_t)w - 1), x1 = (size_t)min(max(ix + 1, 0), (int32_t)w - 1);
+    const size_t y0 = (size_t)min(max(iy, 0), (int32_t)h - 1), y1 = (size_t)min(max(iy + 1, 0), (int32_t)h - 1);
+    const float a = src[y0 * w + x0], b = src[y0 * w + x1], c = src[y1 * w + x0], e = src[y1 * w + x1];
+    const float top = a + (b - a) * tx, bot = c + (e - c) * tx;
+    dst[n] = (top + (bot - top) * ty) * scale + bias;
+}
+
 // One whole view at pixel stride s: output pixel (y, x) of the h x w grid is source pixel (y s, x s), its ray goes through that pixel's
 // centre.  dirs (optional): safe_normalize(d) (nerf/utils.py) of every pixel repeated ssaa x ssaa times, i.e. the nearest upscale to
 // [h ssaa, w ssaa] the stage-1 renderer shades with (nerf/renderer.py:821-828).
@@ -159,6 +220,32 @@ extern "C" int n2m_batch_rays_u8(const float* poses, const float* uniforms, uint
     batch_rays_u8_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W, fx, fy, cx, cy, bank, lut, aabb,
                                                                                 min_near, rays_o, rays_d, rgba, nears, fars, noises, bg, counter,
                                                                                 cam_near_far);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int n2m_batch_rays_u8_depth(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
+                                       float cx, float cy, const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb,
+                                       float min_near, float* rays_o, float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg,
+                                       float* gt_depth, int32_t* counter, const float* cam_near_far, void* stream) {
+    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(bank); N2M_NOTNULL(depth_bank); N2M_NOTNULL(lut); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o);
+    N2M_NOTNULL(rays_d); N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises); N2M_NOTNULL(gt_depth);
+    N2M_REQUIRE(V >= 1 && H >= 1 && W >= 1 && (uint64_t)H * W < (1ull << 24), N2M_EINVAL,
+                "batch_rays_u8_depth: need V >= 1 and 1 <= H*W < 2^24 (pixel index from an fp32 uniform)");
+    if (N == 0) return 0;
+    batch_rays_u8_depth_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W, fx, fy, cx, cy, bank, depth_bank,
+                                                                                      lut, aabb, min_near, rays_o, rays_d, rgba, nears, fars, noises,
+                                                                                      bg, gt_depth, counter, cam_near_far);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int n2m_depth_bank_fill(const float* src, uint32_t h, uint32_t w, uint32_t H, uint32_t W, float ry, float rx, float scale, float bias,
+                                   float* dst, void* stream) {
+    N2M_NOTNULL(src); N2M_NOTNULL(dst);
+    N2M_REQUIRE(h >= 1 && w >= 1 && H >= 1 && W >= 1 && h < (1u << 24) && w < (1u << 24) && (uint64_t)H * W < (1ull << 32), N2M_EINVAL,
+                "depth_bank_fill: need 1 <= h, w < 2^24 and 1 <= H*W < 2^32");
+    depth_bank_fill_kernel<<<n2m_ceil_div((uint64_t)H * W, 256), 256, 0, (hipStream_t)stream>>>(src, h, w, H, W, ry, rx, scale, bias, dst);
     N2M_CHECK_LAUNCH();
     return 0;
 }

@@ -125,7 +125,10 @@ class Stage0Engine:
             self.cam_near_far = capture.cam_near_far
         # --enable_sparse_depth: one batch in ten is all keypoints of one view (capture.DepthSchedule, the same sequence as Stage0Trainer's); the
         # ray buffers are sized for the largest view from the start
-        from .capture import depth_schedule_for
+        from .capture import dense_depth_for, depth_schedule_for
+        # --enable_dense_depth: EVERY batch gathers a depth target beside its colour (n2m_batch_rays_u8_depth) and every step runs the depth
+        # head with weight 1; N stays num_rays, so these steps steer adaptive_num_rays like plain ones.  One rank is what is tested.
+        self.dense_depth = dense_depth_for(capture, opt)
         self.depth_schedule = depth_schedule_for(capture, opt, seed + rank)
         self._depth_rays = 0 if self.depth_schedule is None else int(max(capture.sparse_depth.counts))
         self._min_rays = max(8192, self._depth_rays)
@@ -322,7 +325,7 @@ class Stage0Engine:
                 and _affine(float(model.bound)) is not None and same_geometry(e1, e2) and e1.embeddings.shape[1] == 1
                 and e2.embeddings.shape[1] == 2 and (sdf or not getattr(opt, "progressive_level", False))
                 and opt.patch_size == 1 and (sdf or model.max_level >= e1.num_levels) and not (sdf and opt.lambda_entropy > 0)
-                and not (sdf and getattr(opt, "enable_sparse_depth", False)))      # the depth term is built for density mode
+                and not (sdf and (getattr(opt, "enable_sparse_depth", False) or getattr(opt, "enable_dense_depth", False))))      # the depth term is built for density mode
 
     @property
     def loss_acc(self):
@@ -414,6 +417,11 @@ class Stage0Engine:
             from .capture import batch_sparse_u8
             batch_sparse_u8(self.poses, cap.bank, cap.lut, b.u, depth_view, cap.sparse_depth, self._aabb, model.min_near, cap.H, cap.W, cap.intrinsics,
                             out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg, b.gtd, b.dw), counter=b.counter, cam_near_far=self.cam_near_far)
+        elif self.dense_depth is not None:
+            from .capture import batch_from_uniforms_u8
+            batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, b.u, self._aabb, model.min_near, cap.H, cap.W, cap.intrinsics,
+                                   out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg, b.gtd), counter=b.counter, cam_near_far=self.cam_near_far,
+                                   dense_depth=self.dense_depth)
         elif cap is not None:
             from .capture import batch_from_uniforms_u8
             batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, b.u, self._aabb, model.min_near, cap.H, cap.W, cap.intrinsics,
@@ -979,10 +987,13 @@ class Stage0Engine:
         if order:
             L.call("n2m_composite_live_counts", _p(w["live"]), _p(w["block_live"]))
         try:
-            if b.depth_view is not None:      # depth step (nerf/utils.py:685-705): the same head + the keypoints' depth term
+            if b.depth_view is not None or self.dense_depth is not None:
+                # depth step (nerf/utils.py:685-705): the same head + the depth term -- the keypoints' depth and weight on a sparse-depth step,
+                # the bank's depth with weight 1 (depth_weight NULL) on every step of a dense-depth run
                 L.call("n2m_composite_loss_train_depth", _p(w["sigma"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb,
                        lam_mask, _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, float(max(opt.lambda_entropy, 0.0)),
-                       None, _p(b.gtd), _p(b.dw), float(opt.lambda_depth * min(1.0, self.global_step / 1000)), 0, s)
+                       None, _p(b.gtd), _p(b.dw) if b.depth_view is not None else None,
+                       float(opt.lambda_depth * min(1.0, self.global_step / 1000)), 0, s)
             else:
                 L.call("n2m_composite_loss_train_ent", _p(w["sigma"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb, lam_mask,
                        _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, float(max(opt.lambda_entropy, 0.0)), s)      # loss value: summed by the scaler kernel

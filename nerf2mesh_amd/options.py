@@ -20,6 +20,7 @@ _DEFAULTS = dict(
     fused_mlp=False,     # opt-in: fused MFMA field kernels (nerf2mesh_amd/fused.py) instead of nn.Linear calls
     enable_cam_near_far=False,     # main.py:40 (colmap mode): clamp every ray to its camera's sparse-point depth range
     enable_sparse_depth=False,     # main.py:41 (colmap mode): one step in ten supervises the depth of one view's sparse keypoints (lambda_depth)
+    enable_dense_depth=False,      # main.py:44 (colmap mode): every ray of every step carries a depth target from the view's calibrated depth map (lambda_depth)
     data_format="nerf",            # main.py:36: "nerf" | "colmap" (tools/train_capture.py; capture.Capture.load_nerf / load_colmap)
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")
 )

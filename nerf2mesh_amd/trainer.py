@@ -112,7 +112,10 @@ class Stage0Trainer:
         if capture is not None:
             self.cam_near_far = capture.cam_near_far
         # --enable_sparse_depth (nerf/colmap_provider.py:510-522, nerf/utils.py:685-705): one step in ten takes all keypoints of one view
-        from .capture import depth_schedule_for
+        from .capture import dense_depth_for, depth_schedule_for
+        # --enable_dense_depth (nerf/colmap_provider.py:281-327, 552-553): every ray of every batch carries a depth target, weight 1; such a
+        # step steers adaptive_num_rays like a plain one.  One rank is what is tested.
+        self.dense_depth = dense_depth_for(capture, opt)
         self.depth_schedule = depth_schedule_for(capture, opt, seed + rank)
         self._depth = None            # (gt_depth, depth_weight) of the batch batch() made last, None for a plain batch
         self._loss_sum = torch.zeros((), device=device)
@@ -169,7 +172,13 @@ class Stage0Trainer:
             self._nears_fars = (nears, fars) if self.cam_near_far is not None else None
             return rays_o, rays_d, rgba, noises, bg
         u = torch.rand(self.num_rays, 6, device=self.device, generator=self.gen)
-        if cap is not None:
+        if self.dense_depth is not None:
+            from .capture import batch_from_uniforms_u8
+            rays_o, rays_d, rgba, nears, fars, noises, bg, gtd = batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, u, self.model.aabb_train,
+                                                                                        self.model.min_near, cap.H, cap.W, cap.intrinsics,
+                                                                                        cam_near_far=self.cam_near_far, dense_depth=self.dense_depth)
+            self._depth = (gtd, None)
+        elif cap is not None:
             from .capture import batch_from_uniforms_u8
             rays_o, rays_d, rgba, nears, fars, noises, bg = batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, u, self.model.aabb_train,
                                                                                    self.model.min_near, cap.H, cap.W, cap.intrinsics,
@@ -222,6 +231,7 @@ class Stage0Trainer:
         rays_o, rays_d, images, ticket, bg_color, noises = self._next
         nears_fars = self._nears_fars                      # of THIS batch (batch() sets it; the overlapped preparation below replaces it)
         depth_gt = self._depth                             # likewise: (gt_depth, depth_weight) of a depth step, else None
+        steers = depth_gt is None or self.dense_depth is not None      # a sparse-depth step (one view's keypoints) does not steer the ray count
         self._next = None
         self.global_step += 1
         self.optimizer.zero_grad(set_to_none=True)
@@ -245,7 +255,7 @@ class Stage0Trainer:
             ticket = raymarching.march_rays_train_finish(ticket)
             M0 = ticket[0].shape[0]
             self.last_num_points = M0
-            if opt.adaptive_num_rays and M0 > 0 and depth_gt is None:        # nerf/utils.py:796-797 (a depth step does not steer the ray count)
+            if opt.adaptive_num_rays and M0 > 0 and steers:                  # nerf/utils.py:796-797 (a sparse-depth step does not steer the ray count)
                 self.num_rays = max(1, int(round((opt.num_points / M0) * self.num_rays)))
             adapted = True
             self._next = self._prepare_overlapped()
@@ -282,7 +292,7 @@ class Stage0Trainer:
         self.last_num_points = M
         self.samples_seen += M
         self.rays_seen += N
-        if opt.adaptive_num_rays and M > 0 and not adapted and depth_gt is None:              # nerf/utils.py:796-797
+        if opt.adaptive_num_rays and M > 0 and not adapted and steers:                        # nerf/utils.py:796-797
             self.num_rays = max(1, int(round((opt.num_points / M) * self.num_rays)))
 
         # TV regulariser (nerf/utils.py:812-821 adds it to the unscaled gradients after backward).  Fast path: hand it to the
