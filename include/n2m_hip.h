@@ -814,6 +814,15 @@ int n2m_batch_rays_u8_depth(const float* poses, const float* uniforms, uint32_t 
                             float cx, float cy, const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb,
                             float min_near, float* rays_o, float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg,
                             float* gt_depth, int32_t* counter, const float* cam_near_far, void* stream);
+/* n2m_batch_rays_u8 / n2m_batch_rays_u8_depth for a set with PER-VIEW intrinsics (capture.Capture.per_view_intrinsics; the reference samples
+ * intrinsics [N,4] per ray, nerf/colmap_provider.py:521,540, nerf/dtu_provider.py:265): intrinsics [V,4] f32 rows (fx, fy, cx, cy), 16-byte
+ * aligned; ray n takes the row of the view it draws from u0.  depth_bank and gt_depth both NULL: the plain batch (seven outputs); both
+ * set: gt_depth as n2m_batch_rays_u8_depth; exactly one of them NULL: N2M_ENULL.  Every output has n2m_batch_rays_u8's arithmetic, operand
+ * for operand: a table of equal rows gives the bits of the shared-intrinsics entry points. */
+int n2m_batch_rays_u8_pv(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, const float* intrinsics,
+                         const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb, float min_near, float* rays_o,
+                         float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth, int32_t* counter,
+                         const float* cam_near_far, void* stream);
 /* One view of the dense-depth bank: dst [H*W] f32 = bilinear(src [h,w] f32) * scale + bias.  cv2.INTER_LINEAR's geometry: source
  * coordinate (x + 0.5) * rx - 0.5 and (y + 0.5) * ry - 0.5 with rx = w / W, ry = h / H rounded to fp32 by the caller, both taps of an axis
  * clamped to the edge, fp32 weights, a + (b - a) * t per axis (columns, then rows), multiply and add unfused: bit for bit

@@ -142,6 +142,7 @@ SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_batch_rays_u8_depth": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp],
+    "n2m_batch_rays_u8_pv": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_depth_bank_fill": [_vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
     "n2m_capture_view": [_vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "n2m_capture_box_downscale": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],

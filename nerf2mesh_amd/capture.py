@@ -9,7 +9,9 @@ csrc/capture.hip gather is therefore bit for bit what the torch statement comput
 Every kernel has its torch statement here (batch_from_uniforms_u8, Capture.view, box_downscale); Python takes it when the tensors are on
 the CPU, like synthetic.batch_from_uniforms, and the GPU tests compare the kernels against it.
 
-One camera model per set (H, W, fx, fy, cx, cy), as in the reference's providers; H != W, fx != fy and an off-centre principal point
+One image size per set (H, W) and either ONE camera model (fx, fy, cx, cy) or a per-view table [V,4] of them (Capture.per_view_intrinsics:
+what COLMAP writes without --single_camera, and what every DTU scan has; the reference keeps intrinsics [N,4] and samples them per ray,
+nerf/colmap_provider.py:165-182, 521, 540; nerf/dtu_provider.py:93-104, 265); H != W, fx != fy and an off-centre principal point
 are allowed.  `mvps` is built FROM those intrinsics (proj_matrix), so the rasteriser of stage 1 and the rays of stage 0 see the same
 camera; the reference's projection (nerf/provider.py:266-276) ignores cx, cy and fl_x, so off-centre its rays and its raster disagree.
 """
@@ -66,7 +68,8 @@ def pack_rgba8(images):
 
 
 def rays_from_pixels(poses, cam_idx, pix_i, pix_j, intrinsics):
-    """synthetic.rays_from_pixels (get_rays, nerf/utils.py:242-290) at intrinsics (fx, fy, cx, cy): pixel column pix_i, row pix_j."""
+    """synthetic.rays_from_pixels (get_rays, nerf/utils.py:242-290) at intrinsics (fx, fy, cx, cy): pixel column pix_i, row pix_j.  Each of the
+    four is a number, or a per-ray fp32 tensor [N] (per-view intrinsics gathered at cam_idx)."""
     fx, fy, cx, cy = intrinsics
     i = pix_i.float() + 0.5
     j = pix_j.float() + 0.5
@@ -83,16 +86,51 @@ def decode_words(words, lut):
     return torch.cat([lut[0][b[:, :3]], lut[1][b[:, 3:]]], -1).view(*words.shape, 4)
 
 
+def intrinsics_table(intrinsics, V, device):
+    """None for the shared form (four numbers); for the table form of a per-view set the fp32 [V,4] tensor on `device`, contiguous (what
+    Capture.intrinsics is: no copy then)."""
+    if not (torch.is_tensor(intrinsics) or isinstance(intrinsics, np.ndarray)) or np.ndim(intrinsics) != 2:
+        return None
+    if tuple(intrinsics.shape) != (V, 4):
+        raise ValueError(f"per-view intrinsics must be [{V},4] (fx, fy, cx, cy per view), not {tuple(intrinsics.shape)}")
+    return torch.as_tensor(intrinsics).to(device=device, dtype=torch.float32).contiguous()
+
+
+def intrinsics_row(intrinsics, view):
+    """(fx, fy, cx, cy) of one view as Python floats: the four numbers of the shared form, or row `view` of a [V,4] table (a table on the
+    device is read back: a driver hands the host copy, Capture.intrinsics_host, or Capture.intrinsics_of(view))."""
+    if (torch.is_tensor(intrinsics) or isinstance(intrinsics, np.ndarray)) and np.ndim(intrinsics) == 2:
+        row = intrinsics[int(view)]
+        return tuple(float(x) for x in (row.cpu() if torch.is_tensor(row) else row))
+    return tuple(float(x) for x in intrinsics)
+
+
 def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None, dense_depth=None):
     """synthetic.batch_from_uniforms with the ground truth gathered from a packed uint8 bank [V,H*W] and decoded through `lut`.  On the GPU
     one kernel (n2m_batch_rays_u8); below it the torch statement of the same arithmetic, taken on the CPU.  dense_depth [V,H*W] fp32
     (Capture.dense_depth, --enable_dense_depth): an eighth tensor gt_depth [N] = dense_depth[view_n, pixel_n] follows the seven (`out`
-    then has eight entries); on the GPU n2m_batch_rays_u8_depth."""
+    then has eight entries); on the GPU n2m_batch_rays_u8_depth.  intrinsics: (fx, fy, cx, cy), or the table form of a per-view set
+    (Capture.intrinsics, fp32 [V,4] beside the poses): ray n takes the row of its view -- on the GPU n2m_batch_rays_u8_pv, with or without
+    a depth bank; on the CPU the same statement with the rows gathered at `cam`."""
     dev = poses.device
     N, V = u.shape[0], poses.shape[0]
-    fx, fy, cx, cy = (float(x) for x in intrinsics)
+    table = intrinsics_table(intrinsics, V, dev)
+    if table is None:
+        fx, fy, cx, cy = (float(x) for x in intrinsics)
     if dense_depth is not None and tuple(dense_depth.shape) != tuple(bank.shape):
         raise ValueError(f"the depth bank is {tuple(dense_depth.shape)}, the image bank {tuple(bank.shape)}")
+    if dev.type == "cuda" and table is not None:
+        from . import _lib as L
+        n_out = 7 if dense_depth is None else 8
+        if out is None:
+            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+            out = (f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3)) + (() if dense_depth is None else (f(N),))
+        o, d, rgba, nears, fars, noises, bg = out[:7]
+        gtd = out[7] if n_out == 8 else None
+        L.call("n2m_batch_rays_u8_pv", L.ptr(poses), L.ptr(u), V, N, H, W, L.ptr(table), L.ptr(bank), L.ptr(dense_depth), L.ptr(lut), L.ptr(aabb),
+               float(min_near), L.ptr(o), L.ptr(d), L.ptr(rgba), L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(gtd), L.ptr(counter),
+               L.ptr(cam_near_far), L.stream())
+        return (o, d, rgba, nears, fars, noises, bg) + (() if gtd is None else (gtd,))
     if dev.type == "cuda" and dense_depth is not None:
         from . import _lib as L
         if out is None:
@@ -114,7 +152,8 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
         return o, d, rgba, nears, fars, noises, bg
     cam = (u[:, 0] * V).long().clamp(max=V - 1)
     pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
-    o, d = rays_from_pixels(poses, cam, pix % W, torch.div(pix, W, rounding_mode="floor"), (fx, fy, cx, cy))
+    o, d = rays_from_pixels(poses, cam, pix % W, torch.div(pix, W, rounding_mode="floor"),
+                            (fx, fy, cx, cy) if table is None else table[cam].unbind(-1))
     inv = 1.0 / d
     lo, hi = (aabb[:3] - o) * inv, (aabb[3:] - o) * inv
     tn, tf = torch.minimum(lo, hi).amax(-1), torch.maximum(lo, hi).amin(-1)
@@ -140,7 +179,7 @@ def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, 
     first, K = sparse_depth.range(v)
     if u.shape[0] != K:
         raise ValueError(f"view {v} has {K} keypoints, the uniforms are for {u.shape[0]} rays")
-    fx, fy, cx, cy = (float(x) for x in intrinsics)
+    fx, fy, cx, cy = intrinsics_row(intrinsics, v)            # one view per batch: a per-view set passes that view's four scalars
     if dev.type == "cuda":
         from . import _lib as L
         if out is None:
@@ -423,6 +462,25 @@ def rotmat_to_quat(R):
     return -q if q[0] < 0 else q
 
 
+def decompose_projection(P):
+    """P [3,4] = s K [R | -R C] (any scale s, either sign) -> K [3,3] upper triangular with a positive diagonal and K[2,2] = 1, R [3,3]
+    world-to-camera with det R = +1, C [3] the camera centre; float64 throughout.  What nerf/dtu_provider.py:49-63 takes from
+    cv2.decomposeProjectionMatrix, by an RQ decomposition of M = P[:,:3] (a QR factorisation of the row-reversed transpose); the signs are
+    fixed afterwards: columns of K / rows of R flipped until K's diagonal is positive, and R negated when its determinant is -1 (that
+    is P -> -P, the same camera).  C = -inv(M) P[:,3] does not depend on either."""
+    P = np.asarray(P, dtype=np.float64)
+    M = P[:3, :3]
+    J = np.eye(3)[::-1]
+    q, r = np.linalg.qr((J @ M).T)                 # J M = r^T q^T  ->  M = (J r^T J) (J q^T)
+    K, R = J @ r.T @ J, J @ q.T
+    S = np.diag(np.where(np.diag(K) < 0, -1.0, 1.0))
+    K, R = K @ S, S @ R
+    if np.linalg.det(R) < 0:
+        R = -R
+    C = -np.linalg.solve(M, P[:3, 3])
+    return K / K[2, 2], R, C
+
+
 def _rotation_between(a, b):
     """The rotation that takes direction a to direction b (Rodrigues; nerf/colmap_provider.py:18-27 `rotmat`, whose random retry for
     opposite directions is replaced by a fixed perpendicular axis)."""
@@ -496,12 +554,33 @@ class Capture:
     dense_depth_samples = None        # keep_model=True: per view [K,3] float64 (host), what was fitted: map at the keypoints, their depth, weight
     colmap = None             # load_colmap(keep_model=True): the reconstruction's points, errors, keypoints and names, as save_colmap takes them
 
-    def __init__(self, poses, bank, H, W, intrinsics, has_alpha=True, linear=False, cam_near_far=None, device=None):
+    per_view_intrinsics = False       # True: `intrinsics` is an fp32 [V,4] tensor on the device (fx, fy, cx, cy per view), `intrinsics_host` its float64 source
+    intrinsics_host = None
+
+    def __init__(self, poses, bank, H, W, intrinsics, has_alpha=True, linear=False, cam_near_far=None, device=None, per_view=None):
+        """intrinsics: (fx, fy, cx, cy), or [V,4] of them.  A table whose rows are all equal collapses to the shared form (every path of a
+        one-camera set stays what it is); per_view=True keeps (or makes) the table form even then, per_view=False refuses differing rows."""
         device = torch.device(device if device is not None else bank.device)
         self.device = device
         self.H, self.W = int(H), int(W)
-        self.intrinsics = tuple(float(x) for x in intrinsics)
         poses_cpu = torch.as_tensor(poses).detach().float().cpu().contiguous()
+        V = poses_cpu.shape[0] if poses_cpu.dim() == 3 else 0
+        intr = (intrinsics.detach().double().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics, dtype=np.float64))
+        if intr.shape == (4,):
+            table = np.tile(intr, (V, 1)) if per_view else None
+        elif intr.shape == (V, 4):
+            equal = bool((intr == intr[0]).all())
+            if per_view is False and not equal:
+                raise ValueError("per_view=False, but the rows of the intrinsics differ")
+            table = intr.copy() if (per_view or not equal) else None
+            intr = intr[0]
+        else:
+            raise ValueError(f"intrinsics must be (fx, fy, cx, cy) or [V,4] = [{V},4] of them, not an array of shape {intr.shape}")
+        if table is None:
+            self.intrinsics = tuple(float(x) for x in intr)
+        else:
+            self.per_view_intrinsics = True
+            self.intrinsics_host = table                                   # float64 [V,4]; each device entry is this rounded once to fp32
         if poses_cpu.dim() != 3 or poses_cpu.shape[1:] != (4, 4):
             raise ValueError("poses must be [V,4,4]")
         if tuple(bank.shape) != (poses_cpu.shape[0], self.H * self.W) or bank.dtype != torch.int32:
@@ -512,14 +591,23 @@ class Capture:
         self.has_alpha, self.linear = bool(has_alpha), bool(linear)
         self.lut = decode_lut(self.linear, device)
         self.cam_near_far = None if cam_near_far is None else torch.as_tensor(cam_near_far).float().to(device).contiguous()
+        if self.per_view_intrinsics:
+            self.intrinsics = torch.from_numpy(self.intrinsics_host.astype(np.float32)).to(device).contiguous()
+            self.mvps = torch.stack([proj_matrix(self.H, self.W, *(float(x) for x in self.intrinsics_host[v])) @ torch.inverse(p)
+                                     for v, p in enumerate(poses_cpu)]).to(device)
+            return
         proj = proj_matrix(self.H, self.W, *self.intrinsics)
         self.mvps = torch.stack([proj @ torch.inverse(p) for p in poses_cpu]).to(device)      # per pose on the host, like synthetic.mvp_matrix
 
+    def intrinsics_of(self, v):
+        """(fx, fy, cx, cy) of view v as Python floats, from the host copy: no device read."""
+        return tuple(float(x) for x in self.intrinsics_host[int(v)]) if self.per_view_intrinsics else self.intrinsics
+
     # ------------------------------------------------------------------------------------------------ constructors
     @classmethod
-    def from_arrays(cls, poses, images_uint8, intrinsics, linear=False, cam_near_far=None, downscale=1, device="cpu"):
-        """poses [V,4,4], images uint8 [V,H,W,3|4] (numpy or torch), intrinsics (fx, fy, cx, cy) of the images as given; downscale=k takes
-        the k x k integer block mean on `device` and divides the intrinsics by k."""
+    def from_arrays(cls, poses, images_uint8, intrinsics, linear=False, cam_near_far=None, downscale=1, device="cpu", per_view=None):
+        """poses [V,4,4], images uint8 [V,H,W,3|4] (numpy or torch), intrinsics (fx, fy, cx, cy) of the images as given, or [V,4] of them (per
+        view; see __init__ for `per_view`); downscale=k takes the k x k integer block mean on `device` and divides the intrinsics by k."""
         images = torch.as_tensor(images_uint8)
         V, H, W, _ = images.shape
         bank, has_alpha = pack_rgba8(images)
@@ -529,8 +617,12 @@ class Capture:
             raise ValueError("downscale must be a positive integer")
         if k > 1:
             bank = box_downscale(bank, H, W, k)
-            H, W, intrinsics = H // k, W // k, tuple(float(x) / k for x in intrinsics)
-        return cls(poses, bank, H, W, intrinsics, has_alpha=has_alpha, linear=linear, cam_near_far=cam_near_far, device=device)
+            if np.ndim(intrinsics) == 2:
+                intrinsics = (intrinsics.detach().double().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics, dtype=np.float64)) / k
+            else:
+                intrinsics = tuple(float(x) / k for x in intrinsics)
+            H, W = H // k, W // k
+        return cls(poses, bank, H, W, intrinsics, has_alpha=has_alpha, linear=linear, cam_near_far=cam_near_far, device=device, per_view=per_view)
 
     @classmethod
     def load_nerf(cls, path, split="train", scale=0.33, offset=(0, 0, 0), downscale=1, linear=False, device="cpu"):
@@ -582,14 +674,17 @@ class Capture:
 
     @classmethod
     def load_colmap(cls, path, split="train", scale=-1, downscale=1, linear=False, enable_cam_center=False, sparse_depth=False, device="cpu",
-                    keep_model=False, dense_depth=False):
+                    keep_model=False, dense_depth=False, per_view_intrinsics=False):
         """A COLMAP reconstruction by the rules of nerf/colmap_provider.py:134-278, 404-435 (own reader of cameras.bin / images.bin /
         points3D.bin, see above; looked for under colmap_sparse/0, sparse/0, colmap).  Image keys sorted, entries without a file under
         images_{downscale}/ (else images/) dropped; poses = inv([R|t]) -> center_poses -> convention flip -> scale (-1: 1 / min |camera
         position|); pts_aabb = box of the scaled points; per kept image the keypoints with a 3D point inside the full-resolution image give
         cam_near_far (min, max depth) and, with sparse_depth=True, the CSR table Capture.sparse_depth.  Every 8th kept image is `val`,
         `train` the rest, `trainval` all.  mask/NAME.png supplies alpha.  Without an images_{downscale} folder the bank's own box downscale
-        is taken (integer downscale that divides the size).  One camera model per set: kept images whose cameras differ are a ValueError.
+        is taken (integer downscale that divides the size).  One camera model per set: kept images whose cameras differ are a ValueError
+        -- unless per_view_intrinsics=True: then they give the table form (Capture.per_view_intrinsics), row n the camera of kept image n
+        divided by `downscale` (nerf/colmap_provider.py:165-182: the same models, distortion ignored); the cameras must still state one image
+        size, which the keypoint test and the rounding of keypoint coordinates use.
         keep_model=True keeps the transformed points, their errors and every kept view's keypoints on the host as Capture.colmap (what
         save_colmap takes to write the set back); training needs none of it, so by default it is dropped.
         dense_depth=True (--enable_dense_depth, :281-327): every view of the split needs depths/<stem of its name>.npy, a 2-D float array of
@@ -625,9 +720,16 @@ class Capture:
             else:
                 raise ValueError(f"unsupported COLMAP camera model: {cam['model']}")
             intr.append((cam["height"], cam["width"]) + tuple(float(x) for x in f4))
+        table = None
         if any(i != intr[0] for i in intr[1:]):
-            raise ValueError(f"the kept images use {len(used)} cameras with different parameters; a Capture holds one camera model per set "
-                             "(per-view intrinsics are not supported)")
+            if not per_view_intrinsics:
+                raise ValueError(f"the kept images use {len(used)} cameras with different parameters; a Capture holds one camera model per set "
+                                 "unless it is loaded with per_view_intrinsics=True (tools/train_capture.py --per_view_intrinsics)")
+            if any(i[:2] != intr[0][:2] for i in intr[1:]):
+                raise ValueError(f"the kept images use cameras of differing image sizes ({sorted({i[:2] for i in intr})} as height x width); "
+                                 "per-view intrinsics still need one image size per set")
+            by_id = dict(zip(used, intr))
+            table = np.array([by_id[ims[k]["camera_id"]][2:] for k in keys], dtype=np.float64) / ds
         h0, w0 = intr[0][:2]
         H, W = int(round(h0 / ds)), int(round(w0 / ds))
         fx, fy, cx, cy = (x / ds for x in intr[0][2:])
@@ -705,7 +807,7 @@ class Capture:
                 raise ValueError(f"the images are {ih} x {iw}, the cameras state {h0} x {w0} at downscale {ds}: only the full-size images "
                                  "with an integer downscale that divides them can be reduced here")
             bank = box_downscale(bank, ih, iw, k)
-        cap = cls(poses[sel].astype(np.float32), bank, H, W, (fx, fy, cx, cy), has_alpha=has_alpha, linear=linear,
+        cap = cls(poses[sel].astype(np.float32), bank, H, W, (fx, fy, cx, cy) if table is None else table[sel], has_alpha=has_alpha, linear=linear,
                   cam_near_far=np.asarray(cnf, dtype=np.float32)[sel], device=device)
         cap.pts_aabb = torch.from_numpy(pts_aabb)
         cap.scale = float(scale)
@@ -738,28 +840,96 @@ class Capture:
         return cap
 
     @classmethod
+    def load_dtu(cls, path, split="train", scale=-1, offset=(0, 0, 0), downscale=1, linear=False, device="cpu"):
+        """A DTU scan in the layout of nerf/dtu_provider.py:80-109, 173-211: cameras_sphere.npz (world_mat_i, scale_mat_i), image/*.png and
+        mask/*.png, each list sorted (a mask carries its image's file name; its first channel is the alpha).  Per image P = (world_mat @
+        scale_mat)[:3,:4] in fp32, as the reference forms it; then -- cv2.decomposeProjectionMatrix is not used here -- decompose_projection
+        in float64: row (K00, K11, K02, K12) of K / K22 and the pose [R^T | C], through nerf_matrix_to_ngp (scale == -1 means 1) and the
+        three axis fixes of :107-109.  Every view has its own K: the set comes back in the table form unless all rows are equal.  `val` is
+        the first frame, `train` the rest, `trainval` / `all` every frame (the reference's test trajectory is not built).  downscale=k: the
+        bank's integer box mean, H // k x W // k, and the rows divided by k -- the reference resizes the images and forgets that division
+        (its rays of a downscaled DTU set use the full-size K)."""
+        if split not in ("train", "val", "trainval", "all"):
+            raise ValueError(f"split must be train, val, trainval or all, not {split!r}")
+        k = int(downscale)
+        if k < 1 or k != downscale:
+            raise ValueError("downscale must be a positive integer")
+        if scale == -1:
+            scale = 1
+        cam_file = os.path.join(path, "cameras_sphere.npz")
+        if not os.path.exists(cam_file):
+            raise FileNotFoundError(f"no cameras_sphere.npz under {path}")
+        names = sorted(f for f in os.listdir(os.path.join(path, "image")) if f.endswith(".png")) if os.path.isdir(os.path.join(path, "image")) else []
+        if not names:
+            raise FileNotFoundError(f"no image/*.png under {path}")
+        rows, poses = [], []
+        with np.load(cam_file) as cams:
+            for idx in range(len(names)):
+                for key in (f"world_mat_{idx}", f"scale_mat_{idx}"):
+                    if key not in cams:
+                        raise ValueError(f"{cam_file} has no {key} ({len(names)} images)")
+                P = (cams[f"world_mat_{idx}"].astype(np.float32) @ cams[f"scale_mat_{idx}"].astype(np.float32))[:3, :4]
+                K, R, C = decompose_projection(P)
+                rows.append((K[0, 0], K[1, 1], K[0, 2], K[1, 2]))
+                pose = np.eye(4, dtype=np.float32)
+                pose[:3, :3] = R.T
+                pose[:3, 3] = C
+                poses.append(nerf_matrix_to_ngp(pose, scale, offset))
+        poses = np.stack(poses)
+        poses[:, :3, 1:3] *= -1
+        poses = poses[:, [1, 0, 2, 3], :]
+        poses[:, 2] *= -1
+        sel = list(range(len(names)))
+        sel = sel[1:] if split == "train" else sel[:1] if split == "val" else sel
+        if not sel:
+            raise ValueError(f"the {split} split of {len(names)} images is empty")
+        images = []
+        for i in sel:
+            im = _read_image(os.path.join(path, "image", names[i]))
+            mname = os.path.join(path, "mask", names[i])
+            if not os.path.exists(mname):
+                raise FileNotFoundError(f"image/{names[i]} has no mask: {mname} is missing")
+            mk = _read_image(mname)
+            if mk.shape[:2] != im.shape[:2]:
+                raise ValueError(f"{mname} is {mk.shape[0]} x {mk.shape[1]}, its image {im.shape[0]} x {im.shape[1]}")
+            images.append(np.concatenate([im[..., :3], mk[..., :1]], -1))
+        if any(im.shape != images[0].shape for im in images):
+            raise ValueError("all images of a set must share one size (per-view image sizes are not supported)")
+        cap = cls.from_arrays(poses[sel], np.stack(images), np.asarray(rows, dtype=np.float64)[sel], linear=linear, downscale=k, device=device)
+        cap.scale = float(scale)
+        return cap
+
+    @classmethod
     def synthetic(cls, poses, scene="lego", H=synthetic.LEGO_HW, W=synthetic.LEGO_HW, intrinsics=None, alpha=True, linear=False,
-                  cam_near_far=None, device=None, chunk=1 << 20):
+                  cam_near_far=None, device=None, chunk=1 << 20, per_view=None):
         """The box scene rendered through synthetic.render_gt at arbitrary intrinsics (default: the lego camera) and quantised with
-        (x * 255 + 0.5).to(uint8); alpha=False composites on white and keeps three channels."""
+        (x * 255 + 0.5).to(uint8); alpha=False composites on white and keeps three channels.  intrinsics [V,4]: every view is rendered at
+        its own row (see __init__ for `per_view`)."""
         poses = torch.as_tensor(poses).float()
         dev = torch.device(device if device is not None else poses.device)
         if intrinsics is None:
             intrinsics = (synthetic.LEGO_FOCAL, synthetic.LEGO_FOCAL, W / 2, H / 2)
-        intr = tuple(float(x) for x in intrinsics)
-        pd, bx = poses.to(dev), synthetic.boxes(dev, scene)
         V = poses.shape[0]
+        if np.ndim(intrinsics) == 2:
+            intr = intrinsics.detach().double().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics, dtype=np.float64)
+            if intr.shape != (V, 4):
+                raise ValueError(f"per-view intrinsics must be [{V},4], not {intr.shape}")
+            rows = [tuple(float(x) for x in r) for r in intr]
+        else:
+            intr = tuple(float(x) for x in intrinsics)
+            rows = [intr] * V
+        pd, bx = poses.to(dev), synthetic.boxes(dev, scene)
         images = torch.empty(V, H * W, 4 if alpha else 3, dtype=torch.uint8, device=dev)
         pix = torch.arange(H * W, device=dev)
         for v in range(V):
             for s in range(0, H * W, chunk):
                 p = pix[s:s + chunk]
-                o, d = rays_from_pixels(pd, torch.full_like(p, v), p % W, torch.div(p, W, rounding_mode="floor"), intr)
+                o, d = rays_from_pixels(pd, torch.full_like(p, v), p % W, torch.div(p, W, rounding_mode="floor"), rows[v])
                 rgba = synthetic.render_gt(o, d, bx)
                 if not alpha:
                     rgba = rgba[:, :3] * rgba[:, 3:] + (1 - rgba[:, 3:])
                 images[v, s:s + chunk] = (rgba * 255 + 0.5).to(torch.uint8)
-        return cls.from_arrays(poses, images.view(V, H, W, -1), intr, linear=linear, cam_near_far=cam_near_far, device=dev)
+        return cls.from_arrays(poses, images.view(V, H, W, -1), intr, linear=linear, cam_near_far=cam_near_far, device=dev, per_view=per_view)
 
     # ------------------------------------------------------------------------------------------------------- access
     def check_device(self, device):
@@ -785,7 +955,8 @@ class Capture:
     def view(self, v, stride=1, dirs_ssaa=0):
         """One whole view at pixel stride `stride` (h = H // stride, w = W // stride, pixel (j * stride, i * stride)): rays_o, rays_d [h*w,3],
         rgba [h*w,4], and with dirs_ssaa >= 1 the unit directions [h*ssaa * w*ssaa, 3] stage 1 shades with (safe_normalize of every pixel's
-        direction, repeated ssaa x ssaa times) -- else None.  On the GPU one kernel (n2m_capture_view)."""
+        direction, repeated ssaa x ssaa times) -- else None.  On the GPU one kernel (n2m_capture_view); a per-view set hands it row v's four
+        scalars from the host copy (no device read)."""
         s, a = int(stride), int(dirs_ssaa)
         h, w = self.H // s, self.W // s
         dev = self.device
@@ -794,12 +965,12 @@ class Capture:
             f = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=dev)
             o, d, rgba = f(h * w, 3), f(h * w, 3), f(h * w, 4)
             dirs = f(h * a * w * a, 3) if a >= 1 else None
-            L.call("n2m_capture_view", L.ptr(self.poses), len(self), int(v), self.H, self.W, s, *self.intrinsics, L.ptr(self.bank), L.ptr(self.lut),
+            L.call("n2m_capture_view", L.ptr(self.poses), len(self), int(v), self.H, self.W, s, *self.intrinsics_of(v), L.ptr(self.bank), L.ptr(self.lut),
                    L.ptr(o), L.ptr(d), L.ptr(rgba), L.ptr(dirs), max(a, 1), L.stream())
             return o, d, rgba, dirs
         jj, ii = torch.meshgrid(torch.arange(h, device=dev) * s, torch.arange(w, device=dev) * s, indexing="ij")
         jj, ii = jj.reshape(-1), ii.reshape(-1)
-        o, d = rays_from_pixels(self.poses, int(v), ii, jj, self.intrinsics)
+        o, d = rays_from_pixels(self.poses, int(v), ii, jj, self.intrinsics_of(v))
         rgba = decode_words(self.bank[int(v)][jj * self.W + ii], self.lut)
         dirs = None
         if a >= 1:
@@ -815,6 +986,8 @@ class Capture:
         """transforms_{split}.json + {split}/r_{v}.png (PIL), such that load_nerf(path, split, scale, offset) gives this set back: the stored
         translation is (t - offset) / scale.  RGB sets are written as 3-channel PNGs."""
         from PIL import Image
+        if self.per_view_intrinsics:
+            raise ValueError("the nerf format states one camera for the whole set; a set with per-view intrinsics is written by save_colmap or save_dtu")
         os.makedirs(os.path.join(path, split), exist_ok=True)
         by = self.bank_bytes().cpu().numpy()
         fx, fy, cx, cy = self.intrinsics
@@ -835,7 +1008,8 @@ class Capture:
         keypoints and names of its Capture.colmap) gives this set back; any other set comes back re-centred by center_poses.  Mirrors
         save_nerf.  points [M,3] in this set's world (numbered from 1 in the file), errors [M] (default 1), keypoints: per view (xy [n,2] in
         pixels, index [n] into `points` or -1) -- default: every point projected into every view it lies in front of and inside of.  One
-        camera (id 1) of `model` PINHOLE or SIMPLE_PINHOLE (needs fx = fy) at the stored size.  depths: one 2-D array per view, of any
+        camera (id 1) of `model` PINHOLE or SIMPLE_PINHOLE (needs fx = fy) at the stored size; a set with per-view intrinsics: one camera
+        per distinct row, every image with the id of its row (load_colmap(..., per_view_intrinsics=True) reads it back).  depths: one 2-D array per view, of any
         size, written as depths/<stem of the view's name>.npy (what load_colmap(dense_depth=True) reads)."""
         from PIL import Image
         points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
@@ -843,11 +1017,14 @@ class Capture:
         ids = np.arange(1, M + 1, dtype=np.int64)
         errors = np.ones(M) if errors is None else np.asarray(errors, dtype=np.float64).reshape(M)
         names = [f"r_{v}.png" for v in range(V)] if names is None else list(names)
-        fx, fy, cx, cy = self.intrinsics
+        # one camera per distinct row (ids from 1 in order of first appearance), every image the id of its row; a shared set: one camera, id 1
+        rows = [self.intrinsics_of(v) for v in range(V)]
+        cam_rows = list(dict.fromkeys(rows))
+        cam_id = {r: n + 1 for n, r in enumerate(cam_rows)}
         if model == "PINHOLE":
-            mid, params = 1, (fx, fy, cx, cy)
-        elif model == "SIMPLE_PINHOLE" and fx == fy:
-            mid, params = 0, (fx, cx, cy)
+            mid, cam_params = 1, [r for r in cam_rows]
+        elif model == "SIMPLE_PINHOLE" and all(r[0] == r[1] for r in cam_rows):
+            mid, cam_params = 0, [(r[0], r[2], r[3]) for r in cam_rows]
         else:
             raise ValueError("save_colmap writes PINHOLE, or SIMPLE_PINHOLE when fx == fy")
         # back to COLMAP's frame: undo the scale, then the convention change (its own inverse on the world side)
@@ -863,6 +1040,7 @@ class Capture:
             keypoints = []
             for v in range(V):
                 pc = (pw - poses[v, :3, 3]) @ poses[v, :3, :3]          # camera coordinates (x right, y down, z forward)
+                fx, fy, cx, cy = rows[v]
                 with np.errstate(divide="ignore", invalid="ignore"):
                     x, y = fx * pc[:, 0] / pc[:, 2] + cx, fy * pc[:, 1] / pc[:, 2] + cy
                 m = (pc[:, 2] > 0) & (x >= 0) & (x < self.W) & (y >= 0) & (y < self.H)
@@ -871,9 +1049,10 @@ class Capture:
         os.makedirs(root, exist_ok=True)
         os.makedirs(os.path.join(path, "images"), exist_ok=True)
         with open(os.path.join(root, "cameras.bin"), "wb") as f:
-            f.write(struct.pack("<Q", 1))
-            f.write(struct.pack("<iiQQ", 1, mid, self.W, self.H))
-            f.write(np.asarray(params, dtype="<f8").tobytes())
+            f.write(struct.pack("<Q", len(cam_rows)))
+            for n, params in enumerate(cam_params):
+                f.write(struct.pack("<iiQQ", n + 1, mid, self.W, self.H))
+                f.write(np.asarray(params, dtype="<f8").tobytes())
         by = self.bank_bytes().cpu().numpy()
         tracks = {}
         with open(os.path.join(root, "images.bin"), "wb") as f:
@@ -882,7 +1061,7 @@ class Capture:
                 Rt = poses[v, :3, :3].T                                  # world-to-camera rotation
                 f.write(struct.pack("<i", v + 1))
                 f.write(np.concatenate([rotmat_to_quat(Rt), -Rt @ poses[v, :3, 3]]).astype("<f8").tobytes())
-                f.write(struct.pack("<i", 1))
+                f.write(struct.pack("<i", cam_id[rows[v]]))
                 f.write(names[v].encode() + b"\0")
                 xy, idx = keypoints[v]
                 xy, idx = np.asarray(xy, dtype=np.float64).reshape(-1, 2), np.asarray(idx, dtype=np.int64).reshape(-1)
@@ -907,3 +1086,29 @@ class Capture:
                 tr = tracks.get(int(ids[m]), [])
                 f.write(struct.pack("<QdddBBBdQ", int(ids[m]), *pw[m], 128, 128, 128, float(errors[m]), len(tr)))
                 f.write(np.asarray(tr, dtype="<i4").tobytes())
+
+    def save_dtu(self, path, scale=1.0, offset=(0, 0, 0)):
+        """Writes the set in the DTU layout (cameras_sphere.npz with world_mat_i = K_i [R_i | -R_i C_i] padded to 4 x 4 and an identity
+        scale_mat_i, float64; image/NNN.png, mask/NNN.png) such that load_dtu(path, "all", scale, offset) gives it back: the bank byte
+        for byte, rows and poses up to the rounding of the fp32 product and its decomposition.  A shared set writes its one K for every
+        view.  Mirrors save_colmap; a set without alpha gets all-255 masks (and comes back with has_alpha)."""
+        from PIL import Image
+        for sub in ("image", "mask"):
+            os.makedirs(os.path.join(path, sub), exist_ok=True)
+        poses = self.poses.double().cpu().numpy().copy()
+        poses[:, 2] *= -1                              # the three axis fixes of load_dtu, undone last to first
+        poses = poses[:, [1, 0, 2, 3], :]
+        poses[:, :3, 1:3] *= -1
+        poses[:, :3, 3] = (poses[:, :3, 3] - np.array(offset, dtype=np.float64)) / scale
+        by = self.bank_bytes().cpu().numpy()
+        mats = {}
+        for v in range(len(self)):
+            fx, fy, cx, cy = self.intrinsics_of(v)
+            K = np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float64)
+            R, C = poses[v, :3, :3].T, poses[v, :3, 3]
+            world = np.eye(4)
+            world[:3, :3], world[:3, 3] = K @ R, -K @ R @ C
+            mats[f"world_mat_{v}"], mats[f"scale_mat_{v}"] = world, np.eye(4)
+            Image.fromarray(np.ascontiguousarray(by[v, :, :, :3])).save(os.path.join(path, "image", f"{v:03d}.png"))
+            Image.fromarray(np.ascontiguousarray(by[v, :, :, 3])).save(os.path.join(path, "mask", f"{v:03d}.png"))
+        np.savez(os.path.join(path, "cameras_sphere.npz"), **mats)

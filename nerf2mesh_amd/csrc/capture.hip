@@ -131,6 +131,50 @@ batch_rays_u8_depth_kernel(const float* __restrict__ poses /*[V,4,4]*/, const fl
     if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
 }
 
+// batch_rays_u8_kernel / batch_rays_u8_depth_kernel for a set with PER-VIEW intrinsics (nerf/colmap_provider.py:521,540, nerf/dtu_provider.py:265):
+// ray n takes row v of intrinsics [V,4] = (fx, fy, cx, cy) -- one 16-byte load at the view index it already has; the table is V x 16 bytes
+// and stays in cache.  depth_bank / gt_depth are both set or both NULL (the plain batch).  Everything else is batch_rays_u8_kernel operand
+// for operand, so a table of equal rows gives its bits.
+__global__ void __launch_bounds__(256)
+batch_rays_u8_pv_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, uint32_t W,
+                        uint32_t HW, const float4* __restrict__ intrinsics /*[V] (fx, fy, cx, cy)*/, const uint32_t* __restrict__ bank /*[V,HW]*/,
+                        const float* __restrict__ depth_bank /*[V,HW] or NULL*/, const float* __restrict__ lut /*[2,256]*/,
+                        const float* __restrict__ aabb, float min_near, float* __restrict__ rays_o, float* __restrict__ rays_d,
+                        float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ noises,
+                        float* __restrict__ bg, float* __restrict__ gt_depth /*[N] or NULL*/, int32_t* __restrict__ counter,
+                        const float* __restrict__ cam_near_far /*[V,2] or NULL*/) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0 && counter) counter[0] = 0;
+    if (n >= N) return;
+    const float* __restrict__ un = u + (size_t)n * 6;
+    const uint32_t v = min(V - 1u, (uint32_t)(un[0] * (float)V)), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
+    const float4 K = intrinsics[v];
+    const float fx = K.x, fy = K.y, cx = K.z, cy = K.w;
+    const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
+    const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
+    const float* __restrict__ P = poses + (size_t)v * 16;
+    float o[3], d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
+        o[k] = P[4 * k + 3];
+        rays_d[(size_t)n * 3 + k] = d[k];
+        rays_o[(size_t)n * 3 + k] = o[k];
+    }
+    const size_t at = (size_t)v * HW + (size_t)p;
+    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = decode_rgba8(bank[at], lut);
+    if (depth_bank) gt_depth[n] = depth_bank[at];
+    float tn, tf;
+    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
+    if (cam_near_far) {
+        tn = fmaxf(tn, cam_near_far[2 * v]);
+        tf = fminf(tf, cam_near_far[2 * v + 1]);
+    }
+    nears[n] = tn; fars[n] = tf;
+    noises[n] = un[2];
+    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
+}
+
 // One view of the dense-depth bank (capture.dense_depth_fill): dst [H,W] = bilinear(src [h,w]) * scale + bias with cv2.INTER_LINEAR's
 // geometry -- source coordinate (x + 0.5) * rx - 0.5 per axis (rx = w / W, ry = h / H as the host rounded them to fp32), the two taps of
 // an axis clamped to the edge, fp32 weights, a + (b - a) * t per axis (columns first), so equal taps give their value exactly.  A thread
@@ -236,6 +280,26 @@ extern "C" int n2m_batch_rays_u8_depth(const float* poses, const float* uniforms
     batch_rays_u8_depth_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W, fx, fy, cx, cy, bank, depth_bank,
                                                                                       lut, aabb, min_near, rays_o, rays_d, rgba, nears, fars, noises,
                                                                                       bg, gt_depth, counter, cam_near_far);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int n2m_batch_rays_u8_pv(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, const float* intrinsics,
+                                    const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb, float min_near,
+                                    float* rays_o, float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth,
+                                    int32_t* counter, const float* cam_near_far, void* stream) {
+    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(intrinsics); N2M_NOTNULL(bank); N2M_NOTNULL(lut); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o);
+    N2M_NOTNULL(rays_d); N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises);
+    N2M_REQUIRE((depth_bank == nullptr) == (gt_depth == nullptr), N2M_ENULL,
+                "batch_rays_u8_pv: depth_bank and gt_depth are both set or both NULL, %s is NULL", depth_bank == nullptr ? "depth_bank" : "gt_depth");
+    N2M_REQUIRE(V >= 1 && H >= 1 && W >= 1 && (uint64_t)H * W < (1ull << 24), N2M_EINVAL,
+                "batch_rays_u8_pv: need V >= 1 and 1 <= H*W < 2^24 (pixel index from an fp32 uniform)");
+    N2M_REQUIRE(((uintptr_t)intrinsics & 15u) == 0, N2M_EINVAL, "batch_rays_u8_pv: intrinsics [V,4] must be 16-byte aligned (one load per ray)");
+    if (N == 0) return 0;
+    batch_rays_u8_pv_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W,
+                                                                                   reinterpret_cast<const float4*>(intrinsics), bank, depth_bank, lut,
+                                                                                   aabb, min_near, rays_o, rays_d, rgba, nears, fars, noises, bg,
+                                                                                   gt_depth, counter, cam_near_far);
     N2M_CHECK_LAUNCH();
     return 0;
 }

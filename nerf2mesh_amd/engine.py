@@ -415,7 +415,8 @@ class Stage0Engine:
         b.depth_view = depth_view
         if depth_view is not None:
             from .capture import batch_sparse_u8
-            batch_sparse_u8(self.poses, cap.bank, cap.lut, b.u, depth_view, cap.sparse_depth, self._aabb, model.min_near, cap.H, cap.W, cap.intrinsics,
+            batch_sparse_u8(self.poses, cap.bank, cap.lut, b.u, depth_view, cap.sparse_depth, self._aabb, model.min_near, cap.H, cap.W,
+                            cap.intrinsics_of(depth_view),       # one view per batch: its four scalars from the host copy (per-view sets too)
                             out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg, b.gtd, b.dw), counter=b.counter, cam_near_far=self.cam_near_far)
         elif self.dense_depth is not None:
             from .capture import batch_from_uniforms_u8

@@ -21,7 +21,9 @@ _DEFAULTS = dict(
     enable_cam_near_far=False,     # main.py:40 (colmap mode): clamp every ray to its camera's sparse-point depth range
     enable_sparse_depth=False,     # main.py:41 (colmap mode): one step in ten supervises the depth of one view's sparse keypoints (lambda_depth)
     enable_dense_depth=False,      # main.py:44 (colmap mode): every ray of every step carries a depth target from the view's calibrated depth map (lambda_depth)
-    data_format="nerf",            # main.py:36: "nerf" | "colmap" (tools/train_capture.py; capture.Capture.load_nerf / load_colmap)
+    data_format="nerf",            # main.py:36: "nerf" | "colmap" | "dtu" (tools/train_capture.py; capture.Capture.load_nerf / load_colmap / load_dtu)
+    per_view_intrinsics=False,     # not a reference option (it always keeps intrinsics [N,4]): a COLMAP set whose images use different cameras is
+                                   # loaded with one (fx, fy, cx, cy) row per view (capture.Capture.per_view_intrinsics); "dtu" implies it
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")
 )
 

@@ -452,11 +452,20 @@ class NeRFRenderer(nn.Module):
     @torch.no_grad()
     def mark_untrained_grid(self, poses, intrinsics, cam_near_far=None, S=64):
         """Marks cells no training camera sees, or that lie outside aabb_train, with -1 (nerf/renderer.py:985-1071).
-        poses [B,4,4] cam2world, intrinsics (fx, fy, cx, cy)."""
-        fx, fy, cx, cy = intrinsics
+        poses [B,4,4] cam2world, intrinsics (fx, fy, cx, cy), or [B,4] of them (a set with per-view intrinsics, capture.Capture.intrinsics):
+        cx / fx and cy / fy are then a column per camera of the chunk -- the quotient taken in float64 and rounded to fp32 once, as the
+        tuple form's is -- and the expression is otherwise the same."""
         dev = self.density_grid.device
         poses = poses.to(dev)
         B = poses.shape[0]
+        per_view = getattr(intrinsics, "ndim", 1) == 2            # a tensor or an array [B,4]; the tuple form has no ndim
+        if per_view:
+            k = torch.as_tensor(intrinsics).to(dev).double()
+            if tuple(k.shape) != (B, 4):
+                raise ValueError(f"per-view intrinsics must be [{B},4], not {tuple(k.shape)}")
+            rx, ry = (k[:, 2] / k[:, 0]).float().unsqueeze(1), (k[:, 3] / k[:, 1]).float().unsqueeze(1)      # [B,1]
+        else:
+            fx, fy, cx, cy = intrinsics
         cells = self._cells().unsqueeze(0)                    # [1,N,3]; already Morton-ordered
         mask_cam = torch.zeros_like(self.density_grid)
         mask_aabb = torch.zeros_like(self.density_grid)
@@ -472,7 +481,10 @@ class NeRFRenderer(nn.Module):
                 cam = cam @ poses[head:tail, :3, :3]
                 z = -cam[:, :, 2]
                 near = self.opt.min_near if cam_near_far is None else cam_near_far[head:tail, 0].unsqueeze(1)
-                seen = (z > near) & (cam[:, :, 0].abs() < cx / fx * z + hgs * 2) & (cam[:, :, 1].abs() < cy / fy * z + hgs * 2)
+                if per_view:
+                    seen = (z > near) & (cam[:, :, 0].abs() < rx[head:tail] * z + hgs * 2) & (cam[:, :, 1].abs() < ry[head:tail] * z + hgs * 2)
+                else:
+                    seen = (z > near) & (cam[:, :, 0].abs() < cx / fx * z + hgs * 2) & (cam[:, :, 1].abs() < cy / fy * z + hgs * 2)
                 mask_cam[cas] += seen.any(0)
         self.density_grid[(mask_cam == 0) | (mask_aabb == 0)] = -1
 

@@ -167,7 +167,7 @@ class Stage0Trainer:
             u = torch.rand(cap.sparse_depth.counts[view], 6, device=self.device, generator=self.gen)
             rays_o, rays_d, rgba, nears, fars, noises, bg, gtd, dw = batch_sparse_u8(self.poses, cap.bank, cap.lut, u, view, cap.sparse_depth,
                                                                                      self.model.aabb_train, self.model.min_near, cap.H, cap.W,
-                                                                                     cap.intrinsics, cam_near_far=self.cam_near_far)
+                                                                                     cap.intrinsics_of(view), cam_near_far=self.cam_near_far)
             self._depth = (gtd, dw)
             self._nears_fars = (nears, fars) if self.cam_near_far is not None else None
             return rays_o, rays_d, rgba, noises, bg

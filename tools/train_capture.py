@@ -1,13 +1,20 @@
 #!/usr/bin/env python3
-"""Both stages on a captured image set in the nerf format (transforms_{train,test}.json or transforms.json + images) or, with
---data_format colmap, on a COLMAP reconstruction (colmap_sparse/0 | sparse/0 | colmap + images[_k]/; capture.Capture.load_colmap):
+"""Both stages on a captured image set in the nerf format (transforms_{train,test}.json or transforms.json + images), with
+--data_format colmap on a COLMAP reconstruction (colmap_sparse/0 | sparse/0 | colmap + images[_k]/; capture.Capture.load_colmap), or with
+--data_format dtu on a DTU scan (cameras_sphere.npz + image/ + mask/; capture.Capture.load_dtu):
 
     tools/train_capture.py PATH --workspace DIR [--iters0 N --iters1 N --downscale k --scale s --bound b --color_space srgb|linear]
-                           [--data_format colmap [--enable_sparse_depth | --enable_dense_depth] [--lambda_depth w] [--enable_cam_near_far] [--enable_cam_center]]
+                           [--data_format colmap [--enable_sparse_depth | --enable_dense_depth] [--lambda_depth w] [--enable_cam_near_far] [--enable_cam_center]
+                                                 [--per_view_intrinsics]]
+                           [--data_format dtu]
 
   colmap: --scale defaults to -1 (1 / the nearest camera's distance), the model's training box is the sparse points' (update_aabb,
   main.py:234-235), --enable_cam_near_far clamps every ray to its view's keypoint depth range, --enable_sparse_depth makes one step in
   ten a depth step, --enable_dense_depth puts a depth target from PATH/depths/NAME.npy on every ray of every step, and the held-out views are the `val` split (every 8th image).
+  --per_view_intrinsics accepts a reconstruction whose images use different cameras (COLMAP without --single_camera): one (fx, fy, cx, cy)
+  row per view.
+  dtu: every view has its own K (per-view intrinsics are implied), --scale defaults to 1, the masks supply alpha, and the held-out view is
+  the `val` split (the first frame).
 
   load (capture.Capture.load_nerf: the train split, and the test split if PATH has one) -> stage 0 (step executor on the uint8 bank)
   -> export_stage0(dataset=capture, clean, decimate) -> stage 1 on that mesh (views from the capture) -> export_stage1(atlas="charts")
@@ -38,8 +45,9 @@ ap.add_argument("--workspace", required=True)
 ap.add_argument("--iters0", type=int, default=30000)
 ap.add_argument("--iters1", type=int, default=10000)
 ap.add_argument("--downscale", type=int, default=1)
-ap.add_argument("--scale", type=float, default=None, help="default: 0.33 (nerf), -1 = automatic (colmap)")
-ap.add_argument("--data_format", choices=["nerf", "colmap"], default="nerf")
+ap.add_argument("--scale", type=float, default=None, help="default: 0.33 (nerf), -1 = automatic (colmap), 1 (dtu)")
+ap.add_argument("--data_format", choices=["nerf", "colmap", "dtu"], default="nerf")
+ap.add_argument("--per_view_intrinsics", action="store_true", help="colmap: one (fx, fy, cx, cy) row per view when the images' cameras differ; dtu implies it")
 ap.add_argument("--enable_sparse_depth", action="store_true")
 ap.add_argument("--enable_dense_depth", action="store_true", help="every step supervises depth from PATH/depths/NAME.npy (calibrated per view)")
 ap.add_argument("--enable_cam_near_far", action="store_true")
@@ -57,9 +65,13 @@ args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(args.seed)
 linear = args.color_space == "linear"
-colmap = args.data_format == "colmap"
+colmap, dtu = args.data_format == "colmap", args.data_format == "dtu"
+if dtu:
+    args.per_view_intrinsics = True
+elif args.per_view_intrinsics and not colmap:
+    ap.error("--per_view_intrinsics needs --data_format colmap or dtu (the nerf format states one camera)")
 if args.scale is None:
-    args.scale = -1 if colmap else 0.33
+    args.scale = -1 if colmap else 1 if dtu else 0.33
 if not colmap and (args.enable_sparse_depth or args.enable_dense_depth or args.enable_cam_near_far or args.enable_cam_center):
     ap.error("--enable_sparse_depth / --enable_dense_depth / --enable_cam_near_far / --enable_cam_center need --data_format colmap (the sparse "
              "points supply them)")
@@ -73,11 +85,13 @@ def clock(label, t0, extra=""):
 
 
 def load(split):
+    if dtu:
+        return Capture.load_dtu(args.path, split=split, scale=args.scale, offset=args.offset, downscale=args.downscale, linear=linear, device=dev)
     if not colmap:
         return Capture.load_nerf(args.path, split=split, scale=args.scale, offset=args.offset, downscale=args.downscale, linear=linear, device=dev)
     c = Capture.load_colmap(args.path, split=split, scale=args.scale, downscale=args.downscale, linear=linear,
                             enable_cam_center=args.enable_cam_center, sparse_depth=args.enable_sparse_depth and split == "train",
-                            dense_depth=args.enable_dense_depth and split == "train", device=dev)
+                            dense_depth=args.enable_dense_depth and split == "train", device=dev, per_view_intrinsics=args.per_view_intrinsics)
     if not args.enable_cam_near_far:
         c.cam_near_far = None
     return c
@@ -85,7 +99,7 @@ def load(split):
 
 t0 = time.perf_counter()
 cap = load("train")
-if colmap:
+if colmap or dtu:
     held = load("val")
 else:
     held = load("test") if os.path.exists(os.path.join(args.path, "transforms_test.json")) else cap
@@ -97,7 +111,7 @@ clock("load", t0, f"{len(cap)} training views {cap.H} x {cap.W} ({cap.nbytes / 1
 opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 1 / 256, iters=args.iters0, fused_mlp=True, scale=args.scale,
                    offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace,
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
-                   enable_cam_near_far=args.enable_cam_near_far,
+                   enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics,
                    lambda_depth=args.lambda_depth)
 model = NeRFNetwork(opt)
 if colmap:
@@ -147,7 +161,7 @@ clock("export_stage1", t0, "files: " + ", ".join(sorted(os.listdir(out_dir))))
 depth_steps = sum(v is not None for v in eng.depth_schedule.log[:args.iters0]) if getattr(eng, "depth_schedule", None) is not None else 0
 if args.enable_dense_depth:
     depth_steps = args.iters0                  # every step carries the depth term
-print(json.dumps({"data_format": args.data_format, "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
+print(json.dumps({"data_format": args.data_format, "per_view_intrinsics": bool(cap.per_view_intrinsics), "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
                   "bank_mb": round(cap.nbytes / 1e6, 3), "iters0": args.iters0, "iters1": args.iters1, "faces": int(f0.shape[0]),
                   "psnr_stage0": float(np.mean(psnr0)), "psnr_stage1": float(np.mean(psnr1)), "export_psnr_vs_stage1": ev["mean"],
                   "export_psnr_per_view": ev["psnr_vs_stage1"]}))
