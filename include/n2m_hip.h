@@ -798,6 +798,10 @@ int n2m_batch_rays_u8(const float* poses, const float* uniforms, uint32_t V, uin
                       float cy, const uint32_t* bank, const float* lut, const float* aabb, float min_near, float* rays_o, float* rays_d,
                       float* rgba, float* nears, float* fars, float* noises, float* bg, int32_t* counter, const float* cam_near_far,
                       void* stream);
+/* views_out [N] i32: the view each ray of the batch drawn from uniforms [N,6] reads -- column 0 through the SAME device function the three
+ * batch kernels (n2m_batch_rays_u8, _u8_depth, _u8_pv) use.  Needed by the per-image appearance codes (--ind_dim, n2m_mlp.h) only; a
+ * sparse-depth batch has one view, which the host knows. */
+int n2m_batch_views(const float* uniforms, uint32_t V, uint32_t N, int32_t* views_out, void* stream);
 /* n2m_batch_rays_u8 for the keypoints of ONE view (sparse-depth supervision, nerf/colmap_provider.py:510-522): coords [Ktot,2] i32 (row, col),
  * kp_depth / kp_weight [Ktot] f32 are the whole CSR table of capture.Capture.sparse_depth, [first, first + K) the entries of `view`.  Ray n goes
  * through the centre of pixel coords[first + n]; uniforms [K,6] supply the march jitter (column 2) and the background (3..5), columns 0, 1

@@ -81,6 +81,45 @@ int n2m_field_backward_train(const float* xyz, const float* dirs, const float* h
                              float* d_w_spec1, float* found_inf, float spec_reg, const float* seed, void* stream);
 uint32_t n2m_field_spec_partials(void);      /* slots the forward writes into spec_sq_partial (512) */
 
+/* ---- per-image appearance codes (--ind_dim of the reference, nerf/renderer.py:356,703,850; nerf/network.py:159-166)
+ * color_net's layer 0 then reads [x(3) | h2(32) | code(D)]: w_color0 is the parameter as nn.Linear stores it, row-major [64, 35 + D] (no
+ * repacked copy), codes is individual_codes [R, D] f32 and sample_view [M] int32 names the row of every sample (values are clamped to
+ * [0, R)); sample_view == NULL means row 0 for every sample, what the reference uses in eval mode, for the export and the texture bake.
+ * Semantics are autocast's like the rest: code and weight columns rounded to fp16, fp32 accumulation, fp16 layer output.  The kernels are
+ * compile-time variants of the plain ones with K widened by one double-K MFMA; with codes == 0 every output equals the plain entry
+ * point's on w_color0[:, :35], bit for bit.  1 <= D <= n2m_field_ind_max_dim() (16), else N2M_EUNSUPPORTED.
+ * Backward: d_w_color0 [64, 35 + D] and d_codes [R, D] f32 are ACCUMULATED into.  d_codes is the exact sum (64-bit fixed point, fp16 values
+ * are multiples of 2^-24) of the per-sample fp16 input gradients, so it does not depend on any order; a row no sample names is not touched.
+ * workspace: n2m_field_ind_workspace_bytes(M, R) bytes, 8-byte aligned, contents irrelevant before and after.  A call whose colour branch
+ * is off (rgb / d_rgb NULL) does not read the codes and runs the plain kernels. */
+uint32_t n2m_field_ind_max_dim(void);
+uint64_t n2m_field_ind_workspace_bytes(uint32_t M, uint32_t R);
+/* sample_view [M] from the marcher's (offset, count) table rays [N,2] and the per-ray view ray_view [N] (n2m_batch_views). */
+int n2m_field_sample_views(const int32_t* rays, const int32_t* ray_view, uint32_t N, uint32_t M, int32_t* sample_view, void* stream);
+int n2m_field_forward_ind(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                          const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                          const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R, uint32_t D,
+                          uint32_t M, int shading, int normalize_dirs, float* sigma, float* rgb, float* specular, void* stream);
+int n2m_field_forward_ind_train(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                                const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                                const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R,
+                                uint32_t D, uint32_t M, int shading, int normalize_dirs, float* sigma, float* rgb, float* specular,
+                                float* spec_sq_partial, void* stream);
+int n2m_field_backward_ind(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                           const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                           const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R, uint32_t D,
+                           uint32_t M, int shading, int normalize_dirs, const float* d_sigma, const float* d_rgb, const float* d_specular,
+                           float* d_h1, void* d_h2, float* d_w_sigma0, float* d_w_sigma1, float* d_w_color0, float* d_w_color1,
+                           float* d_w_color2, float* d_w_spec0, float* d_w_spec1, float* d_codes, void* workspace, uint64_t workspace_bytes,
+                           float* found_inf, void* stream);
+int n2m_field_backward_ind_train(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                                 const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                                 const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R,
+                                 uint32_t D, uint32_t M, int shading, int normalize_dirs, const float* d_sigma, const float* d_rgb,
+                                 const float* d_specular, float* d_h1, void* d_h2, float* d_w_sigma0, float* d_w_sigma1, float* d_w_color0,
+                                 float* d_w_color1, float* d_w_color2, float* d_w_spec0, float* d_w_spec1, float* d_codes, void* workspace,
+                                 uint64_t workspace_bytes, float* found_inf, float spec_reg, const float* seed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

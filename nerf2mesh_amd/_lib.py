@@ -138,6 +138,7 @@ SIGNATURES = {
     "n2m_batch_rays": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_batch_rays_cnf": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_batch_rays_u8": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_batch_views": [_vp, _u32, _u32, _vp, _vp],
     "n2m_batch_rays_sparse_u8": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_batch_rays_u8_depth": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -169,6 +170,13 @@ SIGNATURES = {
     "n2m_field_forward_train": [_vp] * 11 + [_u32, _int, _int] + [_vp] * 5,
     "n2m_field_backward_train": [_vp] * 11 + [_u32, _int, _int] + [_vp] * 13 + [_f32, _vp, _vp],
     "n2m_field_spec_partials": [],
+    "n2m_field_ind_max_dim": [],
+    "n2m_field_ind_workspace_bytes": [_u32, _u32],
+    "n2m_field_sample_views": [_vp, _vp, _u32, _u32, _vp, _vp],
+    "n2m_field_forward_ind": [_vp] * 13 + [_u32, _u32, _u32, _int, _int] + [_vp] * 4,
+    "n2m_field_forward_ind_train": [_vp] * 13 + [_u32, _u32, _u32, _int, _int] + [_vp] * 5,
+    "n2m_field_backward_ind": [_vp] * 13 + [_u32, _u32, _u32, _int, _int] + [_vp] * 14 + [_u64, _vp, _vp],
+    "n2m_field_backward_ind_train": [_vp] * 13 + [_u32, _u32, _u32, _int, _int] + [_vp] * 14 + [_u64, _vp, _f32, _vp, _vp],
     # include/n2m_raster.h
     "n2m_rasterize_forward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp],
     "n2m_rasterize_backward": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
@@ -211,7 +219,8 @@ SIGNATURES = {
 }
 
 RESTYPES = {"n2m_occupancy_update_partials": _u32, "n2m_grid_binned_workspace_bytes": _u64, "n2m_grid_binned_pair_workspace_bytes": _u64, "n2m_march_fused_workspace_bytes": _u64,
-            "n2m_marching_cubes_workspace_bytes": _u64, "n2m_field_spec_partials": _u32}   # everything else returns an int status
+            "n2m_marching_cubes_workspace_bytes": _u64, "n2m_field_spec_partials": _u32, "n2m_field_ind_max_dim": _u32,
+            "n2m_field_ind_workspace_bytes": _u64}   # everything else returns an int status
 
 F32, F16 = 0, 1
 ADAM_MAX = 16

@@ -170,6 +170,24 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
     return seven if dense_depth is None else seven + (dense_depth[cam, pix],)
 
 
+def batch_views(u, V, out=None):
+    """int32 [N]: the view every ray of the batch drawn from the uniforms u [N,6] reads -- column 0 through the expression the batch
+    kernels use (n2m_batch_views shares their device function; on the CPU the statement of batch_from_uniforms_u8).  Needed by the
+    per-image appearance codes (--ind_dim) only; a sparse-depth batch has one view: torch.full((K,), view)."""
+    N = u.shape[0]
+    if u.device.type == "cuda":
+        from . import _lib as L
+        if out is None:
+            out = torch.empty(N, dtype=torch.int32, device=u.device)
+        L.call("n2m_batch_views", L.ptr(u), int(V), N, L.ptr(out), L.stream())
+        return out[:N]
+    cam = (u[:, 0] * V).long().clamp(max=V - 1).to(torch.int32)
+    if out is not None:
+        out[:N].copy_(cam)
+        return out[:N]
+    return cam
+
+
 def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None):
     """The depth-bearing batch of ONE view (nerf/colmap_provider.py:510-522): a ray through the centre of every keypoint of `view` in the
     CSR table `sparse_depth` (SparseDepth), jitter and background from u [K_v,6] (columns 2 and 3..5).  Returns batch_from_uniforms_u8's

@@ -12,6 +12,16 @@ __device__ __forceinline__ float4 decode_rgba8(uint32_t word, const float* __res
     return make_float4(lut[word & 255u], lut[(word >> 8) & 255u], lut[(word >> 16) & 255u], lut[256u + (word >> 24)]);
 }
 
+// The view a batch's uniform names: ONE expression for the batch kernels below and for batch_views_kernel, so that the view a ray read its
+// pixel from and the view its appearance code is taken from cannot drift apart.
+__device__ __forceinline__ uint32_t view_of_uniform(float u0, uint32_t V) { return min(V - 1u, (uint32_t)(u0 * (float)V)); }
+
+// views_out[n] = the view ray n of the batch drawn from `u` reads (per-image appearance codes, --ind_dim; launched only then)
+__global__ void __launch_bounds__(256) batch_views_kernel(const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, int32_t* __restrict__ views_out) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n < N) views_out[n] = (int32_t)view_of_uniform(u[(size_t)n * 6], V);
+}
+
 // batch_rays_kernel with the ground truth read from the packed bank: one 4-byte load per ray instead of a 16-byte one
 __global__ void __launch_bounds__(256)
 batch_rays_u8_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, uint32_t W,
@@ -24,7 +34,7 @@ batch_rays_u8_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* _
     if (n == 0 && counter) counter[0] = 0;
     if (n >= N) return;
     const float* __restrict__ un = u + (size_t)n * 6;
-    const uint32_t v = min(V - 1u, (uint32_t)(un[0] * (float)V)), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
+    const uint32_t v = view_of_uniform(un[0], V), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
     const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
     const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
     const float* __restrict__ P = poses + (size_t)v * 16;
@@ -105,7 +115,7 @@ batch_rays_u8_depth_kernel(const float* __restrict__ poses /*[V,4,4]*/, const fl
     if (n == 0 && counter) counter[0] = 0;
     if (n >= N) return;
     const float* __restrict__ un = u + (size_t)n * 6;
-    const uint32_t v = min(V - 1u, (uint32_t)(un[0] * (float)V)), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
+    const uint32_t v = view_of_uniform(un[0], V), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
     const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
     const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
     const float* __restrict__ P = poses + (size_t)v * 16;
@@ -147,7 +157,7 @@ batch_rays_u8_pv_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float
     if (n == 0 && counter) counter[0] = 0;
     if (n >= N) return;
     const float* __restrict__ un = u + (size_t)n * 6;
-    const uint32_t v = min(V - 1u, (uint32_t)(un[0] * (float)V)), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
+    const uint32_t v = view_of_uniform(un[0], V), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
     const float4 K = intrinsics[v];
     const float fx = K.x, fy = K.y, cx = K.z, cy = K.w;
     const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
@@ -300,6 +310,15 @@ extern "C" int n2m_batch_rays_u8_pv(const float* poses, const float* uniforms, u
                                                                                    reinterpret_cast<const float4*>(intrinsics), bank, depth_bank, lut,
                                                                                    aabb, min_near, rays_o, rays_d, rgba, nears, fars, noises, bg,
                                                                                    gt_depth, counter, cam_near_far);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int n2m_batch_views(const float* uniforms, uint32_t V, uint32_t N, int32_t* views_out, void* stream) {
+    N2M_NOTNULL(uniforms); N2M_NOTNULL(views_out);
+    N2M_REQUIRE(V >= 1, N2M_EINVAL, "batch_views: need V >= 1");
+    if (N == 0) return 0;
+    batch_views_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(uniforms, V, N, views_out);
     N2M_CHECK_LAUNCH();
     return 0;
 }

@@ -110,6 +110,62 @@ struct FieldArgs {
 };
 constexpr int kSpecPartials = 512;      // >= the largest forward grid (2 x 256 workgroups)
 
+// ---------------------------------------------------------------------------------------------- per-image appearance codes (--ind_dim)
+// color_net's layer 0 reads [x | h2 | code(D)]: the *_ind entry points run the same kernels with K widened -- the code of a sample's view
+// occupies K blocks 5 and 6 (logical features 40 .. 40 + D, D <= 16) and goes through ONE extra 32x32x16 MFMA per M block behind the five
+// blocks of the plain kernel, whose instruction sequence is kept: zero codes add exact zeros, every other bit stays.  Why K and not a
+// per-view start value of the accumulators: the backward then needs nothing new for d W0[:, 35:] -- the consumer wave's 64 x 64 tile
+// already spans logical columns 40..55, which the plain kernel feeds zeros -- and d code comes out of the transposed image's rows 40..55,
+// which the C0T image (64 rows) already has.  Only the forward image needs a wider pitch: a second copy [64][64 + 4] in LDS the plain
+// kernels leave unused.  Everything here is a compile-time variant (IND): the plain instantiations do not see any of it.
+constexpr int kIndMax = 16;                       // code columns one extra double-K MFMA holds
+constexpr int P_C0X = 68;                         // wide forward image of color_net layer 0: [64][64 + 4]
+constexpr int C0X_HALVES = 64 * P_C0X;
+constexpr int O_C0X_FWD = FWD_HALVES;             // forward kernel: behind its images
+constexpr int O_C0X_BWD = BWD_PC_TILES_HALVES;    // producer/consumer backward: behind the tile buffers, inside the 128 KB it has anyway
+static_assert(O_C0X_BWD + C0X_HALVES <= BWD_PC_HALVES, "the wide layer-0 image must fit the backward's LDS");
+constexpr int kDwTotalInd = 7648 + 64 * kIndMax;  // a workgroup's partial row: the plain 7 648 sums, then d W0[:, 35 + j] as [64][16]
+struct IndArgs {
+    const float* codes;      // [R, D] fp32
+    const int32_t* view;     // [M] row of `codes` per sample (clamped to [0, R)), NULL = row 0 for every sample
+    int D, R;
+    _Float16* d_code;        // backward: [16][M] per-sample gradient of the code columns (fp16 like autocast's input gradient)
+};
+struct FieldArgsInd : FieldArgs { IndArgs ind; };
+template <bool IND> struct ArgsOf { typedef FieldArgs type; };
+template <> struct ArgsOf<true> { typedef FieldArgsInd type; };
+// logical feature k of the wide image -> column of the [64, 35 + D] weight (or -1)
+__device__ __forceinline__ int col_color0_ind(int k, int D) { return k < 32 ? 3 + k : (k < 35 ? k - 32 : (k >= 40 && k < 40 + D ? k - 5 : -1)); }
+// wide forward image (and, TR, the transposed image in the plain kernel's place) of color_net layer 0 from the [64, 35 + D] parameter
+template <bool TR>
+__device__ __forceinline__ void stage_color0_ind(_Float16* wide, _Float16* tr, const float* __restrict__ W, int D) {
+    const int in = 35 + D;
+    for (int idx = threadIdx.x; idx < 64 * 64; idx += blockDim.x) {
+        const int m = idx >> 6, k = idx & 63;
+        const int c = col_color0_ind(k, D);
+        const _Float16 h = (_Float16)(c >= 0 ? W[m * in + c] : 0.0f);
+        wide[m * P_C0X + k] = h;
+        if (TR) tr[k * P_C0T + m] = h;
+    }
+    __syncthreads();
+}
+// the code columns of sample s as the two K-block fragments (blocks 5, 6): lane (n, g) holds codes 4g + i and 8 + 4g + i
+__device__ __forceinline__ void code_frags(const IndArgs& x, uint32_t s, bool valid, int g, h4 (&bc)[2]) {
+    const h4 z = {(_Float16)0, (_Float16)0, (_Float16)0, (_Float16)0};
+    bc[0] = z; bc[1] = z;
+    if (!valid) return;
+    int v = x.view ? x.view[s] : 0;
+    v = min(max(v, 0), x.R - 1);
+    const float* __restrict__ c = x.codes + (size_t)v * x.D;
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int j = 8 * q + 4 * g + i;
+            if (j < x.D) bc[q][i] = (_Float16)c[j];
+        }
+}
+
 // Staging, fast form.  stage_w / stage_wt above walk the PADDED image and fetch one weight per iteration (integer division, a
 // dependent global load, a 2-byte LDS store: ~46 serial round trips per thread, 8-20 us of every launch).  Here every thread first
 // requests its share of the 7 648 real weights (coalesced, all loads in flight at once), the image area is cleared with 16-byte
@@ -141,12 +197,12 @@ __device__ __forceinline__ void w_place(const WRegs<NT, OUT, IN>& r, _Float16* f
         }
     }
 }
-template <int NT, bool TR, bool DO_DENSITY, bool DO_COLOR>
+template <int NT, bool TR, bool DO_DENSITY, bool DO_COLOR, bool IND = false>
 __device__ __forceinline__ void stage_images(_Float16* lds, const FieldArgs& a) {
     WRegs<NT, 32, 19> s0; WRegs<NT, 1, 32> s1; WRegs<NT, 64, 35> c0; WRegs<NT, 64, 64> c1; WRegs<NT, 6, 64> c2; WRegs<NT, 32, 6> p0; WRegs<NT, 3, 32> p1;
     const bool spec = DO_COLOR && a.shading != 0;
     if (DO_DENSITY) { w_fetch(s0, a.w[0]); w_fetch(s1, a.w[1]); }
-    if (DO_COLOR) { w_fetch(c0, a.w[2]); w_fetch(c1, a.w[3]); w_fetch(c2, a.w[4]); }
+    if (DO_COLOR) { if (!IND) w_fetch(c0, a.w[2]); w_fetch(c1, a.w[3]); w_fetch(c2, a.w[4]); }
     if (spec) { w_fetch(p0, a.w[5]); w_fetch(p1, a.w[6]); }
     const uint4 z = make_uint4(0u, 0u, 0u, 0u);
     for (int i = threadIdx.x; i < (TR ? ALL_W_HALVES : FWD_HALVES) / 8; i += NT) reinterpret_cast<uint4*>(lds)[i] = z;
@@ -156,7 +212,7 @@ __device__ __forceinline__ void stage_images(_Float16* lds, const FieldArgs& a) 
         w_place<NT, 1, 32, PERM_PLAIN, TR>(s1, lds + O_S1, P_S1, lds + O_S1T, P_S1T);
     }
     if (DO_COLOR) {
-        w_place<NT, 64, 35, PERM_COLOR0, TR>(c0, lds + O_C0, P_C0, lds + O_C0T, P_C0T);
+        if (!IND) w_place<NT, 64, 35, PERM_COLOR0, TR>(c0, lds + O_C0, P_C0, lds + O_C0T, P_C0T);
         w_place<NT, 64, 64, PERM_PLAIN, TR>(c1, lds + O_C1, P_C1, lds + O_C1T, P_C1T);
         w_place<NT, 6, 64, PERM_PLAIN, TR>(c2, lds + O_C2, P_C2, lds + O_C2T, P_C2T);
     }
@@ -400,12 +456,13 @@ __device__ __forceinline__ void dir_frag(const FieldArgs& a, const RawTile& r, P
 }
 
 // ================================================================================================== forward
-template <bool DO_DENSITY, bool DO_COLOR>
-__global__ void __launch_bounds__(256) field_forward_kernel(FieldArgs a) {
+template <bool DO_DENSITY, bool DO_COLOR, bool IND = false>
+__global__ void __launch_bounds__(256) field_forward_kernel(typename ArgsOf<IND>::type a) {
     // These kernels run beside the next batch's marcher (second stream): their waves win the SIMD's issue arbitration
     __builtin_amdgcn_s_setprio(3);
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
-    stage_images<256, false, DO_DENSITY, DO_COLOR>(lds, a);
+    stage_images<256, false, DO_DENSITY, DO_COLOR, IND>(lds, a);
+    if constexpr (IND) stage_color0_ind<false>(lds + O_C0X_FWD, nullptr, a.w[2], a.ind.D);
 
     const int lane = threadIdx.x & 63, n = lane & 31, g = lane >> 5;
     const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
@@ -433,9 +490,16 @@ __global__ void __launch_bounds__(256) field_forward_kernel(FieldArgs a) {
             h4 b0[5];
             color_frags(cur, b0);
             f16x d1[2] = {zero16(), zero16()};
+            h4 bc[2];
+            if constexpr (IND) code_frags(a.ind, s, valid, g, bc);
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb)
+            for (int mb = 0; mb < 2; ++mb) {
+                if constexpr (IND) {    // the plain kernel's five K blocks in its order, then the code blocks
+                    d1[mb] = mm_k<5>(lds + O_C0X_FWD, P_C0X, mb, b0, d1[mb], lane);
+                    d1[mb] = MFMA16(cat8(ld_a(lds + O_C0X_FWD, P_C0X, mb, 5, lane), ld_a(lds + O_C0X_FWD, P_C0X, mb, 6, lane)), cat8(bc[0], bc[1]), d1[mb]);
+                } else
                 d1[mb] = mm_k<5>(lds + O_C0, P_C0, mb, b0, d1[mb], lane);
+            }
             const h4 b1[8] = {relu_pack<0>(d1[0]), relu_pack<1>(d1[0]), relu_pack<2>(d1[0]), relu_pack<3>(d1[0]),
                               relu_pack<0>(d1[1]), relu_pack<1>(d1[1]), relu_pack<2>(d1[1]), relu_pack<3>(d1[1])};
             f16x d2[2] = {zero16(), zero16()};
@@ -887,11 +951,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 // share a SIMD and each hides the other's MFMA -> convert -> MFMA dependency stalls -- the single-wave kernel above spends 40 % of its
 // cycles in issue stalls with nobody to switch to.  Same arithmetic in the same order per tile: results are bit-identical per
 // accumulator; only the order in which tiles reach an accumulator (hence fp32 rounding of dW) differs with the tile-to-wave map.
-template <bool DO_DENSITY, bool DO_COLOR>
-__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) field_backward_pc_kernel(FieldArgs a) {
+template <bool DO_DENSITY, bool DO_COLOR, bool IND = false>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) field_backward_pc_kernel(typename ArgsOf<IND>::type a) {
     __builtin_amdgcn_s_setprio(3);
     extern __shared__ __attribute__((aligned(16))) _Float16 lds[];
-    stage_images<512, true, DO_DENSITY, DO_COLOR>(lds, a);
+    stage_images<512, true, DO_DENSITY, DO_COLOR, IND>(lds, a);
+    if constexpr (IND) stage_color0_ind<true>(lds + O_C0X_BWD, lds + O_C0T, a.w[2], a.ind.D);
 
     const int lane = threadIdx.x & 63, n = lane & 31, g = lane >> 5, wid = threadIdx.x >> 6;
     const int pair = wid & 3;
@@ -962,12 +1027,19 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         if (DO_COLOR) {   // ---------------------------------------------------------------------------- colour + specular
             h4 b0[5];
             h4 wC0[2][5], wC1[2][8], wC2[1][8];
-            ld_layer(wC0, lds + O_C0, P_C0, lane);
+            h4 bc[2];                                                 // IND: the code blocks of layer 0 (K blocks 5, 6)
+            if constexpr (IND) { ld_layer(wC0, lds + O_C0X_BWD, P_C0X, lane); code_frags(a.ind, s, valid, g, bc); }
+            else ld_layer(wC0, lds + O_C0, P_C0, lane);
             color_frags(cur, b0);
             ld_layer(wC1, lds + O_C1, P_C1, lane);
             __builtin_amdgcn_sched_barrier(0);                       // keep the reads above the MFMAs they are meant to hide behind
             f16x d1[2] = {zero16(), zero16()};
             mm_layer(d1, wC0, b0);
+            if constexpr (IND) {
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+                    d1[mb] = MFMA16(cat8(ld_a(lds + O_C0X_BWD, P_C0X, mb, 5, lane), ld_a(lds + O_C0X_BWD, P_C0X, mb, 6, lane)), cat8(bc[0], bc[1]), d1[mb]);
+            }
             ld_layer(wC2, lds + O_C2, P_C2, lane);
             __builtin_amdgcn_sched_barrier(0);
             const h4 b1[8] = {relu_pack<0>(d1[0]), relu_pack<1>(d1[0]), relu_pack<2>(d1[0]), relu_pack<3>(d1[0]),
@@ -1067,8 +1139,25 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
             // layer 1: dW = dy1^T x X0 ; d h2 = rows 0..31 of W1^T dy1
             // stage C0
 #pragma unroll
-            for (int kb = 0; kb < 8; ++kb) { tile_put(TY(st), kb, dy1[kb], lane); tile_put(TX(st), kb, kb < 5 ? b0[kb] : zero4(), lane); }
+            for (int kb = 0; kb < 8; ++kb) {
+                tile_put(TY(st), kb, dy1[kb], lane);
+                if constexpr (IND) tile_put(TX(st), kb, kb < 5 ? b0[kb] : (kb < 7 ? bc[kb - 5] : zero4()), lane);
+                else tile_put(TX(st), kb, kb < 5 ? b0[kb] : zero4(), lane);
+            }
             __syncthreads(); ++st;
+            if constexpr (IND) {
+                // d code of the sample = rows 40 .. 40 + D of W0^T dy1 (M block 1 of the transposed image), rounded to fp16 like the
+                // gradient of a Linear input under autocast; field_code_grad_kernel sums the samples of a view
+                f16x ec = zero16();
+                ec = mm_k<8>(lds + O_C0T, P_C0T, 1, dy1, ec, lane);
+                if (valid) {
+#pragma unroll
+                    for (int r = 4; r < 12; ++r) {
+                        const int j = 8 * ((r >> 2) - 1) + 4 * g + (r & 3);
+                        if (j < a.ind.D) a.ind.d_code[(size_t)j * Mz + s] = (_Float16)ec[r];
+                    }
+                }
+            }
             f16x e0v[1] = {zero16()};
             mm_layer(e0v, wC0T, dy1);
             const f16x e0 = e0v[0];
@@ -1106,7 +1195,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     // ---------------------------------------------------------------------------- reduce dW: registers -> LDS -> HBM
     __syncthreads();
     float* stage = reinterpret_cast<float*>(lds);        // weights are dead now; 64 x 64 floats fit in the weight area
-    float* const part_row = a.dw_partial + (size_t)blockIdx.x * kDwTotal;
+    float* const part_row = a.dw_partial + (size_t)blockIdx.x * (IND ? kDwTotalInd : kDwTotal);
     if (a.dbg & 2) return;
     // every consumer wave leaves its tiles in its own LDS copy (plain stores), the workgroup sums the four copies in wave order and
     // stores the row.  Two rounds: the two 64 x 64 layers (4 x 2 x 16 KB = 128 KB of the dead LDS), then the five small ones (96 KB).
@@ -1120,6 +1209,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         put(gC1, 0, 64, 64, 8192); put(gC0, 4096, 64, 64, 8192);
         __syncthreads();
         sum(0, 8192, 64, 3, 64, 64, 64, PERM_PLAIN); sum(4096, 8192, 64, 2, 64, 35, 35, PERM_COLOR0);
+        if constexpr (IND) {      // logical columns 40..55 of the same tile: d W0[:, 35 + j], the four copies in wave order
+            for (int idx = threadIdx.x; idx < 64 * kIndMax; idx += blockDim.x) {
+                const float* p = stage + 4096 + (idx >> 4) * 64 + 40 + (idx & 15);
+                part_row[kDwTotal + idx] = ((p[0] + p[8192]) + p[2 * 8192]) + p[3 * 8192];
+            }
+        }
         __syncthreads();
     }
     constexpr int kSmall = 6144;       // C2 32x64 | S1 | S0 | P1 | P0 (32x32 each)
@@ -1136,6 +1231,94 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     if (DO_DENSITY) { sum(2048, kSmall, 32, 1, 1, 32, 32, PERM_PLAIN); sum(3072, kSmall, 32, 0, 32, 19, 19, PERM_SIGMA0); }
 }
 
+// dw_finalize_kernel for the partial rows of the IND backward: the plain 7 648 sums land in the [64, 35 + D] layout of color_net's layer 0,
+// the [64][16] tail of a row is d W0[:, 35 + j].  Same fixed order: sixteen interleaved slices per element, then slice 0..15.
+__global__ void __launch_bounds__(1024) dw_finalize_ind_kernel(const float* __restrict__ part, uint32_t n_rows, DwOut o, uint32_t mask, int D, float* found_inf) {
+    __shared__ float sm[16][64];
+    const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
+    const int e = blockIdx.x * 64 + lane;
+    int mat = 0;
+#pragma unroll
+    for (int i = 1; i < 7; ++i) mat += e >= kDwOff[i] ? 1 : 0;
+    int at = e - kDwOff[mat];                            // offset inside the destination tensor
+    bool live = e < kDwTotal && ((mask >> mat) & 1u);
+    if (e >= kDwTotal) {
+        const int x = e - kDwTotal, j = x & 15;
+        mat = 2; at = (x >> 4) * (35 + D) + 35 + j;
+        live = e < kDwTotalInd && j < D && ((mask >> 2) & 1u);
+    } else if (mat == 2) at = (at / 35) * (35 + D) + at % 35;
+    float acc = 0.f;
+    if (live) {
+        float v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t w = (uint32_t)slice + 16u * i;
+            v[i] = w < n_rows ? part[(size_t)w * kDwTotalInd + e] : 0.f;
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc += v[i];
+    }
+    sm[slice][lane] = acc;
+    __syncthreads();
+    if (slice == 0 && live) {
+        float v = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) v += sm[i][lane];
+        if (v != 0.f) {
+            o.dw[mat][at] += v;
+            if (!(fabsf(v) <= 3.0e38f) && found_inf) *found_inf = 1.0f;
+        }
+    }
+}
+
+// d codes [R, D] from the per-sample fp16 gradients [16][M].  An fp16 value is an integer multiple of 2^-24 below 2^16, so value * 2^24 is
+// an integer below 2^40 and the sum over a batch (< 2^22 samples) fits a 64-bit integer EXACTLY: integer atomics in any order give the same
+// bits.  A thread walks 32 consecutive samples of one code column and adds once per run of equal views (samples are ordered by ray, a ray
+// has one view); field_code_finish_kernel turns the sums into fp32 and adds them to d_codes.  A row no sample names keeps its integer 0 and
+// is not touched.
+__global__ void __launch_bounds__(256) field_code_grad_kernel(const _Float16* __restrict__ d_code, const int32_t* __restrict__ view, uint32_t M, int D,
+                                                              int R, long long* __restrict__ acc, float* found_inf) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    const int j = (int)(t & 15u);
+    const uint32_t s0 = (t >> 4) * 32u;
+    if (j >= D || s0 >= M) return;
+    const uint32_t s1 = min(M, s0 + 32u);
+    long long run = 0;
+    int cur = -1;
+    for (uint32_t s = s0; s < s1; ++s) {
+        int v = view ? view[s] : 0;
+        v = min(max(v, 0), R - 1);
+        if (v != cur) {
+            if (run != 0) atomicAdd((unsigned long long*)(acc + (size_t)cur * 16 + j), (unsigned long long)run);
+            cur = v; run = 0;
+        }
+        const float f = (float)d_code[(size_t)j * M + s];
+        if (fabsf(f) <= 65504.f) run += (long long)(f * 16777216.f);
+        else if (found_inf) *found_inf = 1.0f;                   // inf / nan: the step is skipped, the value is left out
+    }
+    if (run != 0) atomicAdd((unsigned long long*)(acc + (size_t)cur * 16 + j), (unsigned long long)run);
+}
+__global__ void __launch_bounds__(256) field_code_finish_kernel(const long long* __restrict__ acc, int D, int R, float* __restrict__ d_codes, float* found_inf) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int v = t >> 4, j = t & 15;
+    if (v >= R || j >= D) return;
+    const long long x = acc[(size_t)v * 16 + j];
+    if (x == 0) return;
+    const float val = (float)((double)x * (1.0 / 16777216.0));
+    d_codes[(size_t)v * D + j] += val;
+    if (!(fabsf(val) <= 3.0e38f) && found_inf) *found_inf = 1.0f;
+}
+// flatten_rays with a value: sample i of ray n (its run [offset, offset + count) of the marcher's table) gets ray_view[n].  One wave per ray.
+__global__ void __launch_bounds__(256) field_sample_views_kernel(const int32_t* __restrict__ rays, const int32_t* __restrict__ ray_view, uint32_t N,
+                                                                 uint32_t M, int32_t* __restrict__ out) {
+    const uint32_t n = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
+    if (n >= N) return;
+    const uint32_t off = (uint32_t)rays[2 * n], cnt = (uint32_t)rays[2 * n + 1];
+    const int32_t v = ray_view[n];
+    for (uint32_t i = lane; i < cnt; i += 64)
+        if (off + i < M) out[off + i] = v;
+}
+
 int check_field(const char* fn, const float* xyz, const float* h1, const float* const* w, bool density, int shading) {
     N2M_REQUIRE(shading >= 0 && shading <= 2, N2M_EINVAL, "%s: shading must be 0 (diffuse), 1 (full) or 2 (specular)", fn);
     N2M_REQUIRE(xyz, N2M_ENULL, "%s: xyz is NULL", fn);
@@ -1144,9 +1327,10 @@ int check_field(const char* fn, const float* xyz, const float* h1, const float* 
 }
 
 // [256][7 648] floats per stream that ever ran a backward (calls on one stream are ordered, so they can share it); never freed
-float* dw_scratch(hipStream_t s) {
+float* dw_scratch(hipStream_t s, bool ind = false) {
     static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, float*> bufs;       // (device, stream): the null stream exists on every device
+    static std::map<std::pair<int, hipStream_t>, float*> plain, wide; // (device, stream): the null stream exists on every device
+    auto& bufs = ind ? wide : plain;                                  // the IND backward's rows are longer: a scratch of its own
     std::lock_guard<std::mutex> lk(mu);
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) return nullptr;
@@ -1154,7 +1338,7 @@ float* dw_scratch(hipStream_t s) {
     auto it = bufs.find(key);
     if (it != bufs.end()) return it->second;
     float* p = nullptr;
-    if (hipMalloc((void**)&p, (size_t)256 * kDwTotal * sizeof(float)) != hipSuccess) return nullptr;
+    if (hipMalloc((void**)&p, (size_t)256 * (ind ? kDwTotalInd : kDwTotal) * sizeof(float)) != hipSuccess) return nullptr;
     bufs[key] = p;
     return p;
 }
@@ -1170,7 +1354,7 @@ uint32_t persistent_grid(uint32_t M) {
 static int field_forward_impl(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
                                  const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
                                  const float* w_spec0, const float* w_spec1, uint32_t M, int shading, int normalize_dirs, float* sigma, float* rgb,
-                                 float* specular, float* spec_sq_partial, void* stream) {
+                                 float* specular, float* spec_sq_partial, void* stream, const IndArgs* ind = nullptr) {
     const float* w[7] = {w_sigma0, w_sigma1, w_color0, w_color1, w_color2, w_spec0, w_spec1};
     const bool density = sigma != nullptr;
     if (int rc = check_field("field_forward", xyz, h1, w, density, shading)) return rc;
@@ -1189,6 +1373,16 @@ static int field_forward_impl(const float* xyz, const float* dirs, const float* 
     hipStream_t s = (hipStream_t)stream;
     N2M_PROF_K(N2M_K_MLP_FWD, s, (double)M * (12 + 64 + 4 + (color ? 64 + 12 + 12 + 12 : 0)));
     const size_t smem = (size_t)FWD_HALVES * 2;
+    if (ind && color) {      // (a density-only call does not read the codes: the plain kernel)
+        FieldArgsInd ai{};
+        static_cast<FieldArgs&>(ai) = a;
+        ai.ind = *ind;
+        const size_t smem_ind = (size_t)(FWD_HALVES + C0X_HALVES) * 2;
+        if (density) N2M_LAUNCH((field_forward_kernel<true, true, true>), persistent_grid(M) * 2, 256, smem_ind, s, ai);
+        else N2M_LAUNCH((field_forward_kernel<false, true, true>), persistent_grid(M) * 2, 256, smem_ind, s, ai);
+        N2M_CHECK_LAUNCH();
+        return 0;
+    }
     if (color && density) N2M_LAUNCH((field_forward_kernel<true, true>), persistent_grid(M) * 2, 256, smem, s, a);
     else if (color) N2M_LAUNCH((field_forward_kernel<false, true>), persistent_grid(M) * 2, 256, smem, s, a);
     else N2M_LAUNCH((field_forward_kernel<true, false>), persistent_grid(M) * 2, 256, smem, s, a);
@@ -1217,7 +1411,8 @@ static int field_backward_impl(const float* xyz, const float* dirs, const float*
                                   const float* w_spec0, const float* w_spec1, uint32_t M, int shading, int normalize_dirs, const float* d_sigma,
                                   const float* d_rgb, const float* d_specular, float* d_h1, void* d_h2, float* d_w_sigma0,
                                   float* d_w_sigma1, float* d_w_color0, float* d_w_color1, float* d_w_color2, float* d_w_spec0,
-                                  float* d_w_spec1, float* found_inf, float spec_reg, const float* seed, void* stream) {
+                                  float* d_w_spec1, float* found_inf, float spec_reg, const float* seed, void* stream,
+                                  const IndArgs* ind = nullptr, float* d_codes = nullptr, long long* code_acc = nullptr) {
     const float* w[7] = {w_sigma0, w_sigma1, w_color0, w_color1, w_color2, w_spec0, w_spec1};
     float* dw[7] = {d_w_sigma0, d_w_sigma1, d_w_color0, d_w_color1, d_w_color2, d_w_spec0, d_w_spec1};
     const bool density = d_sigma != nullptr;
@@ -1238,6 +1433,8 @@ static int field_backward_impl(const float* xyz, const float* dirs, const float*
         (void)hipFuncSetAttribute((const void*)field_backward_pc_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_PC_HALVES * 2);
         (void)hipFuncSetAttribute((const void*)field_backward_pc_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_PC_HALVES * 2);
         (void)hipFuncSetAttribute((const void*)field_backward_pc_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_PC_HALVES * 2);
+        (void)hipFuncSetAttribute((const void*)field_backward_pc_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_PC_HALVES * 2);
+        (void)hipFuncSetAttribute((const void*)field_backward_pc_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BWD_PC_HALVES * 2);
         attr_set = true;
     }
     FieldArgs a{};
@@ -1251,6 +1448,31 @@ static int field_backward_impl(const float* xyz, const float* dirs, const float*
     hipStream_t s = (hipStream_t)stream;
     N2M_PROF_K(N2M_K_MLP_BWD, s, (double)M * (12 + 64 + 4 + 64 + (color ? 64 + 12 + 24 + 64 : 0)));
     static const bool single_wave = getenv("N2M_FIELD_BWD_SINGLE") != nullptr;     // A/B switch: the one-wave-per-SIMD kernel
+    if (ind && color) {      // (a density-only call does not read the codes: the plain kernels below)
+        const size_t smem = (size_t)BWD_PC_HALVES * 2;
+        const uint32_t grid = persistent_grid(M);
+        float* part = dw_scratch(s, true);
+        N2M_REQUIRE(part != nullptr, (int)hipErrorOutOfMemory, "field_backward_ind: no memory for the weight-gradient scratch");
+        a.dw_partial = part;
+        FieldArgsInd ai{};
+        static_cast<FieldArgs&>(ai) = a;
+        ai.ind = *ind;
+        if (hipMemsetAsync(code_acc, 0, (size_t)ind->R * 16 * sizeof(long long), s) != hipSuccess) return N2M_EINVAL;
+        if (density) N2M_LAUNCH((field_backward_pc_kernel<true, true, true>), grid, 512, smem, s, ai);
+        else N2M_LAUNCH((field_backward_pc_kernel<false, true, true>), grid, 512, smem, s, ai);
+        N2M_CHECK_LAUNCH();
+        DwOut o;
+        for (int i = 0; i < 7; ++i) o.dw[i] = dw[i];
+        const uint32_t mask = (density ? 0x03u : 0u) | 0x1Cu | (shading != 0 ? 0x60u : 0u);
+        N2M_LAUNCH(dw_finalize_ind_kernel, (kDwTotalInd + 63) / 64, 1024, 0, s, part, grid, o, mask, ind->D, found_inf);
+        N2M_CHECK_LAUNCH();
+        N2M_LAUNCH(field_code_grad_kernel, n2m_ceil_div((uint64_t)n2m_ceil_div(M, 32) * 16, 256), 256, 0, s, ind->d_code, ind->view, M, ind->D, ind->R,
+                   code_acc, found_inf);
+        N2M_CHECK_LAUNCH();
+        N2M_LAUNCH(field_code_finish_kernel, n2m_ceil_div((uint64_t)ind->R * 16, 256), 256, 0, s, code_acc, ind->D, ind->R, d_codes, found_inf);
+        N2M_CHECK_LAUNCH();
+        return 0;
+    }
     if (!single_wave) {
         const size_t smem = (size_t)BWD_PC_HALVES * 2;
         const uint32_t grid = persistent_grid(M);
@@ -1295,4 +1517,72 @@ extern "C" int n2m_field_backward_train(const float* xyz, const float* dirs, con
     return field_backward_impl(xyz, dirs, h1, h2, w_sigma0, w_sigma1, w_color0, w_color1, w_color2, w_spec0, w_spec1, M, shading, normalize_dirs,
                                d_sigma, d_rgb, d_specular, d_h1, d_h2, d_w_sigma0, d_w_sigma1, d_w_color0, d_w_color1, d_w_color2, d_w_spec0,
                                d_w_spec1, found_inf, spec_reg, seed, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ per-image appearance codes (--ind_dim)
+static int check_ind(const char* fn, const float* codes, uint32_t R, uint32_t D) {
+    N2M_REQUIRE(D >= 1 && D <= (uint32_t)kIndMax, N2M_EUNSUPPORTED, "%s: ind_dim %u is outside 1..%d (the code columns of one double-K MFMA)", fn, D, kIndMax);
+    N2M_REQUIRE(codes != nullptr, N2M_ENULL, "%s: codes is NULL", fn);
+    N2M_REQUIRE(R >= 1 && R < (1u << 24), N2M_EINVAL, "%s: need 1 <= R < 2^24 code rows", fn);
+    return 0;
+}
+extern "C" uint32_t n2m_field_ind_max_dim(void) { return (uint32_t)kIndMax; }
+extern "C" uint64_t n2m_field_ind_workspace_bytes(uint32_t M, uint32_t R) {
+    return (((uint64_t)16 * M * sizeof(_Float16) + 255) & ~(uint64_t)255) + (uint64_t)R * 16 * sizeof(long long);
+}
+extern "C" int n2m_field_sample_views(const int32_t* rays, const int32_t* ray_view, uint32_t N, uint32_t M, int32_t* sample_view, void* stream) {
+    N2M_NOTNULL(rays); N2M_NOTNULL(ray_view); N2M_NOTNULL(sample_view);
+    if (N == 0 || M == 0) return 0;
+    field_sample_views_kernel<<<n2m_ceil_div((uint64_t)N * 64, 256), 256, 0, (hipStream_t)stream>>>(rays, ray_view, N, M, sample_view);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
+extern "C" int n2m_field_forward_ind_train(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                                           const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                                           const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R,
+                                           uint32_t D, uint32_t M, int shading, int normalize_dirs, float* sigma, float* rgb, float* specular,
+                                           float* spec_sq_partial, void* stream) {
+    if (int rc = check_ind("field_forward_ind", codes, R, D)) return rc;
+    IndArgs ind{codes, sample_view, (int)D, (int)R, nullptr};
+    return field_forward_impl(xyz, dirs, h1, h2, w_sigma0, w_sigma1, w_color0, w_color1, w_color2, w_spec0, w_spec1, M, shading, normalize_dirs,
+                              sigma, rgb, specular, spec_sq_partial, stream, &ind);
+}
+extern "C" int n2m_field_forward_ind(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                                     const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                                     const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R, uint32_t D,
+                                     uint32_t M, int shading, int normalize_dirs, float* sigma, float* rgb, float* specular, void* stream) {
+    return n2m_field_forward_ind_train(xyz, dirs, h1, h2, w_sigma0, w_sigma1, w_color0, w_color1, w_color2, w_spec0, w_spec1, codes, sample_view, R, D,
+                                       M, shading, normalize_dirs, sigma, rgb, specular, nullptr, stream);
+}
+extern "C" int n2m_field_backward_ind_train(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                                            const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                                            const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R,
+                                            uint32_t D, uint32_t M, int shading, int normalize_dirs, const float* d_sigma, const float* d_rgb,
+                                            const float* d_specular, float* d_h1, void* d_h2, float* d_w_sigma0, float* d_w_sigma1, float* d_w_color0,
+                                            float* d_w_color1, float* d_w_color2, float* d_w_spec0, float* d_w_spec1, float* d_codes, void* workspace,
+                                            uint64_t workspace_bytes, float* found_inf, float spec_reg, const float* seed, void* stream) {
+    if (int rc = check_ind("field_backward_ind", codes, R, D)) return rc;
+    IndArgs ind{codes, sample_view, (int)D, (int)R, nullptr};
+    long long* acc = nullptr;
+    if (d_rgb != nullptr) {
+        N2M_REQUIRE(d_codes != nullptr && workspace != nullptr, N2M_ENULL, "field_backward_ind: d_codes / workspace is NULL");
+        N2M_REQUIRE(workspace_bytes >= n2m_field_ind_workspace_bytes(M, R) && ((uintptr_t)workspace & 7u) == 0, N2M_EINVAL,
+                    "field_backward_ind: the workspace needs n2m_field_ind_workspace_bytes(M, R) bytes, 8-byte aligned");
+        ind.d_code = (_Float16*)workspace;
+        acc = (long long*)((char*)workspace + (((uint64_t)16 * M * sizeof(_Float16) + 255) & ~(uint64_t)255));
+    }
+    return field_backward_impl(xyz, dirs, h1, h2, w_sigma0, w_sigma1, w_color0, w_color1, w_color2, w_spec0, w_spec1, M, shading, normalize_dirs,
+                               d_sigma, d_rgb, d_specular, d_h1, d_h2, d_w_sigma0, d_w_sigma1, d_w_color0, d_w_color1, d_w_color2, d_w_spec0,
+                               d_w_spec1, found_inf, spec_reg, seed, stream, &ind, d_codes, acc);
+}
+extern "C" int n2m_field_backward_ind(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
+                                      const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
+                                      const float* w_spec0, const float* w_spec1, const float* codes, const int32_t* sample_view, uint32_t R, uint32_t D,
+                                      uint32_t M, int shading, int normalize_dirs, const float* d_sigma, const float* d_rgb, const float* d_specular,
+                                      float* d_h1, void* d_h2, float* d_w_sigma0, float* d_w_sigma1, float* d_w_color0, float* d_w_color1,
+                                      float* d_w_color2, float* d_w_spec0, float* d_w_spec1, float* d_codes, void* workspace, uint64_t workspace_bytes,
+                                      float* found_inf, void* stream) {
+    return n2m_field_backward_ind_train(xyz, dirs, h1, h2, w_sigma0, w_sigma1, w_color0, w_color1, w_color2, w_spec0, w_spec1, codes, sample_view, R, D,
+                                        M, shading, normalize_dirs, d_sigma, d_rgb, d_specular, d_h1, d_h2, d_w_sigma0, d_w_sigma1, d_w_color0,
+                                        d_w_color1, d_w_color2, d_w_spec0, d_w_spec1, d_codes, workspace, workspace_bytes, found_inf, 0.f, nullptr, stream);
 }

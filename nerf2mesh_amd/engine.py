@@ -66,6 +66,7 @@ class _RayBufs:
         self.depth_view = None                  # the view of a depth batch, None for a plain one
         self.u = self.bg = None
         self.rays = torch.empty(cap, 2, dtype=torch.int32, device=dev)
+        self.views = None            # int32 [cap]: the view of every ray (individual codes only: Stage0Engine._prepare allocates it)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ws = torch.empty(int(L.lib().n2m_march_fused_workspace_bytes(cap)), dtype=torch.uint8, device=dev)   # chunk records, group totals
         self.one_pass = False        # samples written by the single-pass marcher (complete once the count is)
@@ -96,9 +97,13 @@ class Stage0Engine:
         assert dev.type == "cuda", "the step executor drives HIP kernels: no CPU path"
         if bool(opt.sdf) and world_size > 1:
             raise ValueError("Stage0Engine runs the SDF recipe on one rank; use trainer.Stage0Trainer for multi-rank SDF training")
-        if not self.supported(model, opt):
-            raise ValueError("Stage0Engine covers the fused recipes (fused_mlp, fp16, no individual codes, power-of-two "
-                             "bound, shared encoder geometry); use trainer.Stage0Trainer for other configurations")
+        self.ind_dim = int(getattr(opt, "ind_dim", 0))
+        if self.ind_dim > 0 and capture is not None and len(capture) > int(opt.ind_num):
+            raise ValueError(f"the capture has {len(capture)} views but ind_num is {int(opt.ind_num)}: every view needs a code row")
+        if not self.supported(model, opt, capture=capture, world_size=world_size):
+            raise ValueError("Stage0Engine covers the fused recipes (fused_mlp, fp16, individual codes only on a capture -- density mode, "
+                             "one rank, ind_dim <= 16 --, power-of-two bound, shared encoder geometry); use trainer.Stage0Trainer for "
+                             "other configurations")
         L.lib()
         self.poses = poses.to(dev).float().contiguous()
         self.rank, self.world = rank, world_size
@@ -198,7 +203,7 @@ class Stage0Engine:
         # [experiment, N2M_LOOKUP_OVERLAP=1, single GPU] Adam in two calls by level half -- fine rows first -- and the NEXT step's lookup of the fine
         # levels on a stream of its own behind the first call: the lookup (L2-request bound) beside the optimizer pass of the coarse rows + the MLP
         # weights (HBM-stream bound).  Same bits (Adam is element-wise, the lookup's levels write disjoint rows).  Measured: see DESIGN section 7.
-        self.lookup_overlap = os.environ.get("N2M_LOOKUP_OVERLAP", "0") == "1" and world_size == 1 and not opt.sdf
+        self.lookup_overlap = os.environ.get("N2M_LOOKUP_OVERLAP", "0") == "1" and world_size == 1 and not opt.sdf and self.ind_dim == 0
         self._fine_ready = None
         if self.lookup_overlap:
             self.s_lookup = L.side_stream(dev, slot=4)
@@ -223,6 +228,10 @@ class Stage0Engine:
         for p in self.mlp_params:
             self.dw_views.append(self.dw[o:o + p.numel()])
             o += p.numel()
+        # per-image codes (--ind_dim): their gradient lives beside the seven dW in a flat buffer of its own, all-zero between steps like
+        # `dw` (the *_ind field backward adds into it, the Adam kernel clears it)
+        self.dcodes = torch.zeros_like(model.individual_codes.data) if self.ind_dim > 0 else None
+        self._ind_ws = None
         self._desc = {}
         self._bufs = [None, None, None]
         self._marker = None
@@ -318,10 +327,14 @@ class Stage0Engine:
 
     # ------------------------------------------------------------------------------------------------ configuration
     @staticmethod
-    def supported(model, opt):
+    def supported(model, opt, capture=None, world_size=1):
         e1, e2 = model.encoder, model.encoder_color
         sdf = bool(opt.sdf)      # SDF recipe (config 5): NeuS alpha, finite-difference normals, eikonal loss, progressive levels -- _step_sdf
-        return (bool(getattr(opt, "fused_mlp", False)) and bool(opt.fp16) and getattr(opt, "ind_dim", 0) == 0
+        # per-image codes (--ind_dim): through the *_ind field kernels on a captured set, density mode, one rank, up to fused.ind_max_dim() columns
+        from .fused import ind_max_dim
+        ind = int(getattr(opt, "ind_dim", 0))
+        ind_ok = ind == 0 or (capture is not None and not sdf and world_size == 1 and ind <= ind_max_dim())
+        return (bool(getattr(opt, "fused_mlp", False)) and bool(opt.fp16) and ind_ok
                 and _affine(float(model.bound)) is not None and same_geometry(e1, e2) and e1.embeddings.shape[1] == 1
                 and e2.embeddings.shape[1] == 2 and (sdf or not getattr(opt, "progressive_level", False))
                 and opt.patch_size == 1 and (sdf or model.max_level >= e1.num_levels) and not (sdf and opt.lambda_entropy > 0)
@@ -382,6 +395,7 @@ class Stage0Engine:
             w["live"] = torch.zeros(cn, dtype=torch.int32, device=dev)
             w["block_live"] = torch.zeros((cn + 15) // 16 + 1, dtype=torch.int32, device=dev)
             w["perm"] = torch.empty(cm, dtype=torch.int32, device=dev)
+            w["sview"] = torch.empty(cm, dtype=torch.int32, device=dev) if self.ind_dim > 0 else None      # code row of every sample
             w["zeros"] = torch.zeros(max(cm, 3 * cn), dtype=torch.float32, device=dev)
             self._work_cap = (cm, cn)
         return self._w
@@ -430,6 +444,15 @@ class Stage0Engine:
         else:
             synthetic.batch_from_uniforms(self.poses, self.images, b.u, self._aabb, model.min_near,
                                           out=(b.o, b.d, b.rgba, b.nears, b.fars, b.noises, b.bg), counter=b.counter, cam_near_far=self.cam_near_far)
+        if self.ind_dim > 0:
+            # which view every ray reads: the same uniforms through the batch kernels' own expression (n2m_batch_views); launched only here
+            if b.views is None or b.views.numel() < b.cap:
+                b.views = torch.empty(b.cap, dtype=torch.int32, device=dev)
+            if depth_view is not None:
+                b.views[:N].fill_(int(depth_view))
+            else:
+                from .capture import batch_views
+                batch_views(b.u, self.poses.shape[0], out=b.views)
         bits = model.density_bitfield
         b.args = (_p(b.o), _p(b.d), _p(bits), float(model.real_bound), int(bool(opt.contract)), float(opt.dt_gamma), int(opt.max_steps), N,
                   int(model.cascade), int(model.grid_size), _p(b.nears), _p(b.fars))
@@ -570,7 +593,10 @@ class Stage0Engine:
         grads = {model.encoder.embeddings: (self.g1, 0, 0, (pk, 2)), model.encoder_color.embeddings: (self.g2, 1, 0, (pk, 3))}
         for i, p in enumerate(self.mlp_params):
             grads[p] = (self.dw_views[i], 0, 1, None)
-        live = set(params[:2]) | set(self.mlp_params[:5]) | (set(self.mlp_params[5:]) if full else set())
+        live = {model.encoder.embeddings, model.encoder_color.embeddings} | set(self.mlp_params[:5]) | (set(self.mlp_params[5:]) if full else set())
+        if self.ind_dim > 0:      # lr x 0.1, no weight decay (renderer.get_params); same found_inf skip as every other tensor of the pass
+            grads[model.individual_codes] = (self.dcodes, 0, 1, None)
+            live.add(model.individual_codes)
         if self.opt.sdf:          # the NeuS variance (lr x 0.1, nerf/network.py:186): its gradient is a scalar the SDF head's backward leaves in d_var
             grads[model.variance] = (self._sdf_buf()["d_var"], 0, 0, None)
             live.add(model.variance)
@@ -974,8 +1000,15 @@ class Stage0Engine:
             # sums of specular^2, the backward adds 2 lambda / M * specular * seed to the recomputed activation's gradient; the [M,3]
             # specular tensor is neither written nor read
             spec_reg = shading != 0 and opt.lambda_specular > 0
-            L.call("n2m_field_forward_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw], M, shading, 1,
-                   _p(w["sigma"]), _p(w["rgb"]), None, _p(w["spec_partial"]) if spec_reg else None, s)
+            if self.ind_dim > 0:
+                codes = model.individual_codes
+                L.call("n2m_field_sample_views", _p(b.rays), _p(b.views), N, M, _p(w["sview"]), s)
+                L.call("n2m_field_forward_ind_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw],
+                       _p(codes), _p(w["sview"]), codes.shape[0], codes.shape[1], M, shading, 1, _p(w["sigma"]), _p(w["rgb"]), None,
+                       _p(w["spec_partial"]) if spec_reg else None, s)
+            else:
+                L.call("n2m_field_forward_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw], M, shading, 1,
+                       _p(w["sigma"]), _p(w["rgb"]), None, _p(w["spec_partial"]) if spec_reg else None, s)
             if want_tv and self.tv_at == 1:
                 start_tv()
         bg_t, bg_s = (bg, 0.0) if random_bg else (None, 1.0)
@@ -1010,9 +1043,19 @@ class Stage0Engine:
                 start_tv()
             if self.marker_at == 2:
                 self._marker = torch.cuda.Event(); self._marker.record()
-            L.call("n2m_field_backward_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw], M, shading, 1,
-                   _p(d_sigma), _p(d_rgb), None, _p(w["d_h1"]), _p(w["d_h2"]), *[_p(g) for g in self.dw_views], _p(o.found_inf),
-                   float(2.0 * opt.lambda_specular / M) if spec_reg else 0.0, _p(seed) if spec_reg else None, s)
+            if self.ind_dim > 0:
+                codes = model.individual_codes
+                need = int(L.lib().n2m_field_ind_workspace_bytes(self._work_cap[0], codes.shape[0]))      # grow-only, sized with the step's buffers
+                if self._ind_ws is None or self._ind_ws.numel() < need:
+                    self._ind_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+                L.call("n2m_field_backward_ind_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw],
+                       _p(codes), _p(w["sview"]), codes.shape[0], codes.shape[1], M, shading, 1, _p(d_sigma), _p(d_rgb), None, _p(w["d_h1"]),
+                       _p(w["d_h2"]), *[_p(g) for g in self.dw_views], _p(self.dcodes), _p(self._ind_ws), self._ind_ws.numel(), _p(o.found_inf),
+                       float(2.0 * opt.lambda_specular / M) if spec_reg else 0.0, _p(seed) if spec_reg else None, s)
+            else:
+                L.call("n2m_field_backward_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw], M, shading, 1,
+                       _p(d_sigma), _p(d_rgb), None, _p(w["d_h1"]), _p(w["d_h2"]), *[_p(g) for g in self.dw_views], _p(o.found_inf),
+                       float(2.0 * opt.lambda_specular / M) if spec_reg else 0.0, _p(seed) if spec_reg else None, s)
             L.grid_backward_config(*self._bwd_cfg)
             need = L.lib().n2m_grid_binned_pair_workspace_bytes(M, self.Lv, self.ho.ctypes.data)
             ws = L.workspace(dev, need)

@@ -125,9 +125,32 @@ def _encode_backward_pair(d_h1, d_h2, x01, emb1, emb2h, net, max_level, in_affin
     return g1, g2
 
 
+class IndCode:
+    """Per-image appearance codes for the fused field (--ind_dim): the parameter `codes` [R, D] and the row every sample reads,
+    `view` int32 [M] -- None: row 0 for every sample (eval, export, texture bake: nerf/renderer.py:356,703,850)."""
+    __slots__ = ("codes", "view")
+
+    def __init__(self, codes, view=None):
+        self.codes, self.view = codes, view
+
+
+def ind_max_dim():
+    """Largest ind_dim the fused field kernels take (include/n2m_mlp.h); larger codes run the unfused network."""
+    return 16
+
+
+def sample_views(rays, ray_view, M):
+    """int32 [M]: the view of every sample from the marcher's (offset, count) table and the per-ray views (n2m_field_sample_views)."""
+    _bind()
+    out = torch.empty(M, dtype=torch.int32, device=rays.device)
+    L.call("n2m_field_sample_views", _p(rays), _p(ray_view), rays.shape[0], M, _p(out), L.stream())
+    return out
+
+
 class _fused_field(Function):
     @staticmethod
-    def forward(ctx, xyz, dirs, emb1, emb2, w0, w1, w2, w3, w4, w5, w6, net, shading, want_color, want_density, normalize_dirs):
+    def forward(ctx, xyz, dirs, emb1, emb2, w0, w1, w2, w3, w4, w5, w6, net, shading, want_color, want_density, normalize_dirs, codes=None,
+                sample_view=None):
         _bind()
         xyz = xyz.float().contiguous()
         M = xyz.shape[0]
@@ -165,8 +188,20 @@ class _fused_field(Function):
             rgb = torch.empty(M, 3, dtype=torch.float32, device=xyz.device)
             spec = torch.empty(M, 3, dtype=torch.float32, device=xyz.device) if shading != 0 else None
         flags = int(bool(normalize_dirs)) | (2 if getattr(net.opt, "sdf", False) else 0)      # bit 1: SDF head, sigma = raw fp16 output
-        L.call("n2m_field_forward", _p(xyz), _p(dirs), _p(h1), _p(h2), *[_p(w) for w in ws], M, shading, flags, _p(sigma), _p(rgb),
-               _p(spec), L.stream())
+        ind = codes is not None and want_color
+        if ind:
+            codes = codes.float().contiguous()
+            if sample_view is not None:
+                sample_view = sample_view.to(torch.int32).contiguous()
+                assert sample_view.shape[0] == M
+            assert ws[2].shape[1] == 35 + codes.shape[1], "color_net layer 0 does not match the code width"
+            L.call("n2m_field_forward_ind", _p(xyz), _p(dirs), _p(h1), _p(h2), *[_p(w) for w in ws], _p(codes), _p(sample_view), codes.shape[0],
+                   codes.shape[1], M, shading, flags, _p(sigma), _p(rgb), _p(spec), L.stream())
+        else:
+            L.call("n2m_field_forward", _p(xyz), _p(dirs), _p(h1), _p(h2), *[_p(w) for w in ws], M, shading, flags, _p(sigma), _p(rgb),
+                   _p(spec), L.stream())
+        ctx.ind, ctx.n_in = ind, 16 + (codes is not None) + (sample_view is not None or codes is not None)
+        ctx.codes, ctx.sample_view = (codes, sample_view) if ind else (None, None)
         ctx.net, ctx.shading, ctx.want_color, ctx.max_level, ctx.want_density = net, shading, want_color, max_level, want_density
         ctx.normalize_dirs = flags
         ctx.bound = bound
@@ -218,8 +253,18 @@ class _fused_field(Function):
             live = [want_density] * 2 + [want_color] * 3 + [want_color and shading != 0] * 2
             prev = amp.get("dw_views") or [None] * 7        # an earlier backward call of the same step (SDF: field + normals) keeps its weights live
             amp["dw_flat"], amp["dw_views"] = flat, [g if (ok or pv is not None) else None for g, ok, pv in zip(dws, live, prev)]
-        L.call("n2m_field_backward", _p(xyz), _p(dirs), _p(h1), _p(h2), *[_p(w) for w in ws], M, shading, ctx.normalize_dirs, _p(d_sigma), _p(d_rgb),
-               _p(d_spec), _p(d_h1), _p(d_h2), *[_p(g) for g in dws], _p(amp["found_inf"]) if amp is not None else None, L.stream())
+        d_codes = None
+        if ctx.ind:
+            codes, view = ctx.codes, ctx.sample_view
+            d_codes = torch.zeros_like(codes)
+            need = int(L.lib().n2m_field_ind_workspace_bytes(M, codes.shape[0]))
+            work = torch.empty(need, dtype=torch.uint8, device=dev)
+            L.call("n2m_field_backward_ind", _p(xyz), _p(dirs), _p(h1), _p(h2), *[_p(w) for w in ws], _p(codes), _p(view), codes.shape[0], codes.shape[1],
+                   M, shading, ctx.normalize_dirs, _p(d_sigma), _p(d_rgb), _p(d_spec), _p(d_h1), _p(d_h2), *[_p(g) for g in dws], _p(d_codes),
+                   _p(work), need, _p(amp["found_inf"]) if amp is not None else None, L.stream())
+        else:
+            L.call("n2m_field_backward", _p(xyz), _p(dirs), _p(h1), _p(h2), *[_p(w) for w in ws], M, shading, ctx.normalize_dirs, _p(d_sigma), _p(d_rgb),
+                   _p(d_spec), _p(d_h1), _p(d_h2), *[_p(g) for g in dws], _p(amp["found_inf"]) if amp is not None else None, L.stream())
         if amp is not None:
             amp["flagged"] = True
         # both tables: one shared fill when their geometry is identical (it is for nerf2mesh), else one backward per table
@@ -266,16 +311,21 @@ class _fused_field(Function):
             dws[5:] = [None] * 2
         if not want_density:
             dws[:2] = [None] * 2
-        return (None, None, g1, g2, *dws, None, None, None, None, None)
+        return (None, None, g1, g2, *dws, None, None, None, None, None) + ((d_codes, None) if ctx.n_in == 18 else ())
 
 
-def fused_field(net, xyz, dirs, shading="full", normalize_dirs=False):
-    """sigma [M], rgb [M,3], specular [M,3] | None -- NeRFNetwork.forward without individual codes.
+def _code_args(c):
+    return () if c is None else (c.codes, c.view)
+
+
+def fused_field(net, xyz, dirs, shading="full", normalize_dirs=False, c=None):
+    """sigma [M], rgb [M,3], specular [M,3] | None -- NeRFNetwork.forward; c: None or the IndCode of the samples (--ind_dim).
     normalize_dirs: `dirs` are raw ray directions and get safe_normalize'd inside the kernel."""
     sh = SHADING[shading]
     out = _fused_field.apply(xyz, dirs, net.encoder.embeddings, net.encoder_color.embeddings, net.sigma_net.net[0].weight,
                              net.sigma_net.net[1].weight, net.color_net.net[0].weight, net.color_net.net[1].weight,
-                             net.color_net.net[2].weight, net.specular_net.net[0].weight, net.specular_net.net[1].weight, net, sh, True, True, normalize_dirs)
+                             net.color_net.net[2].weight, net.specular_net.net[0].weight, net.specular_net.net[1].weight, net, sh, True, True, normalize_dirs,
+                             *_code_args(c))
     if sh == 0:
         return out[0], out[1], None
     return out
@@ -288,10 +338,11 @@ def fused_density(net, xyz):
                               net.color_net.net[2].weight, net.specular_net.net[0].weight, net.specular_net.net[1].weight, net, 0, False, True, False)
 
 
-def fused_color(net, xyz, dirs, shading="full"):
-    """rgb [M,3], specular [M,3] | None -- NeRFNetwork.rgb without individual codes (stage 1: nerf/renderer.py:875-881)."""
+def fused_color(net, xyz, dirs, shading="full", c=None):
+    """rgb [M,3], specular [M,3] | None -- NeRFNetwork.rgb (stage 1: nerf/renderer.py:875-881); c: None or an IndCode."""
     sh = SHADING[shading]
     out = _fused_field.apply(xyz, dirs, net.encoder.embeddings, net.encoder_color.embeddings, net.sigma_net.net[0].weight,
                              net.sigma_net.net[1].weight, net.color_net.net[0].weight, net.color_net.net[1].weight,
-                             net.color_net.net[2].weight, net.specular_net.net[0].weight, net.specular_net.net[1].weight, net, sh, True, False, False)
+                             net.color_net.net[2].weight, net.specular_net.net[0].weight, net.specular_net.net[1].weight, net, sh, True, False, False,
+                             *_code_args(c))
     return (out[0], None) if sh == 0 else (out[0], out[1])

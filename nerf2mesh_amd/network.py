@@ -99,13 +99,33 @@ class NeRFNetwork(NeRFRenderer):
 
     def _can_fuse(self, c=None):
         # SDF: the fused kernels return the raw fp16 sigma_net output (flag bit 1); progressive levels go through max_level
-        return bool(getattr(self.opt, "fused_mlp", False)) and c is None and x_is_cuda(self)
+        if not (bool(getattr(self.opt, "fused_mlp", False)) and x_is_cuda(self)):
+            return False
+        if c is None:
+            return True
+        # per-image codes: the *_ind kernels take an IndCode (parameter + per-sample row) of up to ind_max_dim() columns, density mode only;
+        # a gathered [M, D] tensor, a wider code or the SDF recipe run the unfused network
+        from .fused import IndCode, ind_max_dim
+        return isinstance(c, IndCode) and 1 <= c.codes.shape[1] <= ind_max_dim() and not self.opt.sdf
+
+    def ind_code(self, view=None):
+        """What forward / rgb / geo_feat take as `c`: the fused kernels' IndCode when they cover this model, else the reference's tensor
+        ([1, D] row 0, or the rows of `view` [M]); None without codes."""
+        if self.individual_dim <= 0:
+            return None
+        from .fused import IndCode
+        probe = IndCode(self.individual_codes, view)
+        if self._can_fuse(probe):
+            return probe
+        return self.individual_codes[[0]] if view is None else self.individual_codes[view.long()]
 
     def forward(self, x, d, c=None, shading="full", raw_dirs=False):
         """raw_dirs: `d` are un-normalised ray directions (only valid when _can_fuse(c): the kernel normalises on load)."""
+        if c is None and self.individual_dim > 0:
+            c = self.ind_code()              # a model with codes evaluated without one: row 0, as the reference's eval mode
         if self._can_fuse(c):
             from .fused import fused_field
-            return fused_field(self, x.view(-1, 3), d.view(-1, 3), shading, normalize_dirs=raw_dirs)
+            return fused_field(self, x.view(-1, 3), d.view(-1, 3), shading, normalize_dirs=raw_dirs, c=c)
         assert not raw_dirs
         sigma = self.density(x)["sigma"]
         color, specular = self.rgb(x, d, c, shading)
@@ -152,6 +172,8 @@ class NeRFNetwork(NeRFRenderer):
         return torch.stack([0.5 * (s[0] - s[1]) / epsilon, 0.5 * (s[2] - s[3]) / epsilon, 0.5 * (s[4] - s[5]) / epsilon], dim=-1)
 
     def geo_feat(self, x, c=None):
+        if c is not None and not torch.is_tensor(c):      # a fused.IndCode: this unfused graph takes the rows themselves
+            c = c.codes[[0]] if c.view is None else c.codes[c.view.long()]
         h = self.encoder_color(x, bound=self.bound, max_level=self.max_level)
         h = torch.cat([x, h], dim=-1)
         if c is not None:
@@ -159,9 +181,11 @@ class NeRFNetwork(NeRFRenderer):
         return torch.sigmoid(self.color_net(h))
 
     def rgb(self, x, d, c=None, shading="full"):
+        if c is None and self.individual_dim > 0:
+            c = self.ind_code()
         if self._can_fuse(c) and not x.requires_grad:
             from .fused import fused_color
-            return fused_color(self, x.reshape(-1, 3), d.reshape(-1, 3), shading)
+            return fused_color(self, x.reshape(-1, 3), d.reshape(-1, 3), shading, c=c)
         geo_feat = self.geo_feat(x, c)
         diffuse = geo_feat[..., :3]
         if shading == "diffuse":

@@ -184,8 +184,13 @@ class NeRFRenderer(nn.Module):
         if bg_color is None:
             bg_color = 1
         ind_code = None
+        fuse_ind = False      # per-image codes through the fused field: the kernel reads the parameter and a per-sample row (fused.IndCode)
         if self.individual_dim > 0:
-            ind_code = self.individual_codes[index] if self.training else self.individual_codes[[0]]
+            fuse_ind = hasattr(self, "ind_code") and not torch.is_tensor(self.ind_code())
+            if fuse_ind:
+                ind_code = self.ind_code()           # row 0 (eval); training: the samples' rows, once the marcher's table is known
+            else:
+                ind_code = self.individual_codes[index.long() if torch.is_tensor(index) else index] if self.training else self.individual_codes[[0]]
         results = {}
         amp = torch.autocast(device_type="cuda", dtype=torch.float16, enabled=bool(self.opt.fp16))
 
@@ -202,7 +207,15 @@ class NeRFRenderer(nn.Module):
                 # this autograd path does not, and says so instead of hanging a multi-rank job half-way through its collectives.
                 raise RuntimeError("render: the batch marched no sample at all (cameras outside the scene / empty occupancy grid); "
                                    "the autograd renderer needs at least one sample -- the step executor handles empty batches")
-            if ind_code is not None and ind_code.shape[0] > 1:
+            if fuse_ind:
+                from .fused import sample_views
+                if index is None:
+                    raise ValueError("render: training with individual codes needs `index`, the view of every ray")
+                idx = torch.as_tensor(index, device=device).reshape(-1).to(torch.int32).contiguous()
+                if idx.numel() not in (1, N):
+                    raise ValueError(f"render: `index` names {idx.numel()} views for {N} rays")
+                ind_code = self.ind_code(sample_views(rays, idx, xyzs.shape[0]) if idx.numel() > 1 else idx.expand(xyzs.shape[0]).contiguous())
+            elif ind_code is not None and ind_code.shape[0] > 1:
                 ind_code = ind_code[raymarching.flatten_rays(rays, xyzs.shape[0]).long()]
             in_kernel = hasattr(self, "_can_fuse") and self._can_fuse(ind_code)      # fused field: safe_normalize happens on load
             if not in_kernel:
@@ -242,10 +255,11 @@ class NeRFRenderer(nn.Module):
 
     def _infer_shade(self, xyzs, dirs, ts, ind_code, shading, amp):
         """Field evaluation of one inference round (nerf/renderer.py:779-794): (sigmas | alphas, rgbs)."""
-        if not self.opt.sdf and ind_code is None and getattr(self, "_can_fuse", lambda c=None: False)(None):
+        if not self.opt.sdf and not torch.is_tensor(ind_code) and getattr(self, "_can_fuse", lambda c=None: False)(ind_code):
             # the fused field kernel normalises the ray directions on load (same arithmetic as safe_normalize): four launches fewer per round
+            # (ind_code: None, or the fused kernels' IndCode without rows -- code row 0 for every sample)
             with amp:
-                sigmas, rgbs, _ = self(xyzs, dirs, None, shading, raw_dirs=True)
+                sigmas, rgbs, _ = self(xyzs, dirs, ind_code, shading, raw_dirs=True)
             return sigmas, rgbs
         dirs = safe_normalize(dirs)
         with amp:
@@ -799,7 +813,7 @@ class NeRFRenderer(nn.Module):
             rays_d = F.interpolate(rays_d.view(1, h0, w0, 3).permute(0, 3, 1, 2), (h, w), mode="nearest").permute(0, 2, 3, 1).reshape(-1, 3).contiguous()
         return safe_normalize(rays_d)
 
-    def _stage1_front(self, rays_d, mvp, h0, w0, shading="full", dirs=None, packed=False, vertices=None):
+    def _stage1_front(self, rays_d, mvp, h0, w0, shading="full", dirs=None, packed=False, vertices=None, index=None):
         """Everything of render_stage1 up to and including the two antialias calls (nerf/renderer.py:816-887): returns
         (rast [1,h,w,4], alpha [1,h,w,1] and rgb [1,h,w,3] as antialias hands them out, BEFORE the clamp).  dirs: stage1_dirs(rays_d, h0, w0)
         when the caller has it already.  packed: ONE antialias call on the [1,h,w,4] image RGB + alpha instead of the reference's two (the
@@ -821,12 +835,17 @@ class NeRFRenderer(nn.Module):
             xyzs = contract(xyzs)
         idx = torch.nonzero(mask_flatten, as_tuple=False).squeeze(1)
         self.last_covered = int(idx.numel())
+        # individual codes (nerf/renderer.py:850): the trained view's row while training, row 0 otherwise -- one row for every covered pixel
+        ind_code = None
+        if self.individual_dim > 0 and hasattr(self, "ind_code"):
+            row = int(index) if (self.training and index is not None) else None
+            ind_code = self.ind_code(None if row is None else torch.full((int(idx.numel()),), row, dtype=torch.int32, device=device))
         if idx.numel() > 0 and xyzs.is_cuda:
             # (the boolean-mask gather / scatter of :875-881 over the index list: torch's index kernels take 50 us per call on 0.7 M rows)
             from .losses import gather_rows, scatter_rows
             pts = gather_rows(xyzs if self.opt.enable_offset_nerf_grad else xyzs.detach(), idx)
             with torch.autocast(device_type="cuda", dtype=torch.float16, enabled=bool(self.opt.fp16)):
-                mask_rgbs, _ = self.rgb(pts, gather_rows(dirs, idx), None, shading)
+                mask_rgbs, _ = self.rgb(pts, gather_rows(dirs, idx), ind_code, shading)
             if packed:
                 rgba = scatter_rows(torch.cat([mask_rgbs.float(), gather_rows(mask.view(-1, 1), idx)], dim=1), idx, h * w).view(1, h, w, 4)
                 return rast, None, dr.antialias(rgba, rast, vertices_clip, self.triangles, pos_gradient_boost=self.opt.pos_gradient_boost)
@@ -835,7 +854,7 @@ class NeRFRenderer(nn.Module):
             rgbs = torch.zeros(h * w, 3, device=device, dtype=torch.float32)
             if idx.numel() > 0:
                 pts = xyzs[idx] if self.opt.enable_offset_nerf_grad else xyzs[idx].detach()
-                mask_rgbs, _ = self.rgb(pts, dirs[idx], None, shading)
+                mask_rgbs, _ = self.rgb(pts, dirs[idx], ind_code, shading)
                 rgbs = rgbs.index_copy(0, idx, mask_rgbs.float())
         rgbs = rgbs.view(1, h, w, 3)
         alphas = mask.float()
@@ -853,7 +872,7 @@ class NeRFRenderer(nn.Module):
             bg_color = 1
         if torch.is_tensor(bg_color) and bg_color.dim() == 2:
             bg_color = bg_color.view(h0, w0, 3)
-        rast, alphas, rgbs = self._stage1_front(rays_d, mvp, h0, w0, shading)
+        rast, alphas, rgbs = self._stage1_front(rays_d, mvp, h0, w0, shading, index=index)
         alphas = alphas.squeeze(0).clamp(0, 1)
         rgbs = rgbs.squeeze(0).clamp(0, 1)
         image = alphas * rgbs

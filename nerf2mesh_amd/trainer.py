@@ -72,7 +72,14 @@ class Stage0Trainer:
         self.gen.manual_seed(seed + rank)
         # main.py:221 Adam(eps=1e-15) + nerf/utils.py:506 GradScaler.  Single GPU with the fused field: optim.FusedAdamAMP does both
         # in two launches and takes the inf/nan verdict from the kernels that produce the gradients.
-        self.amp_adam = device.type == "cuda" and bool(getattr(opt, "fused_mlp", False)) and bool(opt.fp16) and getattr(opt, "ind_dim", 0) == 0
+        # (per-image codes, --ind_dim: their gradient reaches FusedAdamAMP through autograd like any unflagged tensor's)
+        self.amp_adam = device.type == "cuda" and bool(getattr(opt, "fused_mlp", False)) and bool(opt.fp16)
+        self.ind_codes = getattr(opt, "ind_dim", 0) > 0
+        if self.ind_codes and capture is None:
+            raise ValueError("individual codes (ind_dim > 0) need a captured image set: the analytic scene has no per-image appearance")
+        if self.ind_codes and len(capture) > opt.ind_num:
+            raise ValueError(f"the capture has {len(capture)} views but ind_num is {opt.ind_num}: every view needs a code row")
+        self._index = None            # int32 [N] view of every ray of the batch batch() made last (ind_dim > 0), else None
         if self.amp_adam:
             from .optim import FusedAdamAMP
             self.optimizer = FusedAdamAMP(model.get_params(opt.lr), eps=1e-15, amp=bool(opt.fp16))
@@ -170,8 +177,13 @@ class Stage0Trainer:
                                                                                      cap.intrinsics_of(view), cam_near_far=self.cam_near_far)
             self._depth = (gtd, dw)
             self._nears_fars = (nears, fars) if self.cam_near_far is not None else None
+            if self.ind_codes:
+                self._index = torch.full((u.shape[0],), int(view), dtype=torch.int32, device=self.device)
             return rays_o, rays_d, rgba, noises, bg
         u = torch.rand(self.num_rays, 6, device=self.device, generator=self.gen)
+        if self.ind_codes:
+            from .capture import batch_views
+            self._index = batch_views(u, len(cap))        # the same draw, the same expression: the views the batch kernel reads
         if self.dense_depth is not None:
             from .capture import batch_from_uniforms_u8
             rays_o, rays_d, rgba, nears, fars, noises, bg, gtd = batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, u, self.model.aabb_train,
@@ -217,7 +229,7 @@ class Stage0Trainer:
         with torch.cuda.stream(side):
             nxt = self._prepare()
         rays_o, rays_d, images, ticket, bg, noises = nxt
-        for t in (self._depth or ()) + (rays_o, rays_d, images, bg, noises, ticket.rays, ticket.counter, ticket.noises) + tuple(ticket.keep) + tuple(ticket.spec or ()):
+        for t in (self._depth or ()) + (self._index,) + (rays_o, rays_d, images, bg, noises, ticket.rays, ticket.counter, ticket.noises) + tuple(ticket.keep) + tuple(ticket.spec or ()):
             if torch.is_tensor(t):
                 t.record_stream(main)          # allocated on the side stream, consumed on the main one
         return nxt
@@ -231,6 +243,7 @@ class Stage0Trainer:
         rays_o, rays_d, images, ticket, bg_color, noises = self._next
         nears_fars = self._nears_fars                      # of THIS batch (batch() sets it; the overlapped preparation below replaces it)
         depth_gt = self._depth                             # likewise: (gt_depth, depth_weight) of a depth step, else None
+        index = self._index                                # likewise: the view of every ray (individual codes), else None
         steers = depth_gt is None or self.dense_depth is not None      # a sparse-depth step (one view's keypoints) does not steer the ray count
         self._next = None
         self.global_step += 1
@@ -261,7 +274,7 @@ class Stage0Trainer:
             self._next = self._prepare_overlapped()
 
         # (without the pipelined march the per-view near / far clamp of --enable_cam_near_far has to reach render() itself)
-        out = model.render(rays_o, rays_d, bg_color=bg_color, perturb=True, shading=shading, dt_gamma=opt.dt_gamma,
+        out = model.render(rays_o, rays_d, index=index, bg_color=bg_color, perturb=True, shading=shading, dt_gamma=opt.dt_gamma,
                            max_steps=opt.max_steps, ticket=ticket, blend_bg=not self.fused_loss,
                            nears_fars=nears_fars if ticket is None else None)
         if self.fused_loss:
@@ -771,7 +784,8 @@ class Stage1Trainer:
             if dirs is None:              # unit directions at the rendered resolution: per view, resident like the rays they come from
                 dirs = self._dirs[v] = model.stage1_dirs(rays_d, self.H, self.W).detach()
             verts = model.vertices + model.vertices_offsets            # once: the front half and the smoothness loss share it
-            rast, aa_alpha, aa_rgb = model._stage1_front(rays_d, self.mvps[v], self.H, self.W, shading, dirs=dirs, packed=self.packed_aa, vertices=verts)
+            rast, aa_alpha, aa_rgb = model._stage1_front(rays_d, self.mvps[v], self.H, self.W, shading, dirs=dirs, packed=self.packed_aa, vertices=verts,
+                                                                index=v if self.capture is not None else None)
             te = (model.triangles_errors, model.triangles_errors_cnt) if opt.refine else (None, None)      # update_triangles_errors rides along
             # (seed: with FusedAdamAMP the total loss is differentiated with gradient = loss scale and this term enters it with weight 1)
             # (multi-GPU: the gradient that flows into the loss is scale / world -- FusedAdamAMP.backward(loss, world) -- and the head must be
@@ -784,7 +798,8 @@ class Stage1Trainer:
         else:
             gt_mask = rgba[:, 3:]
             gt_rgb = rgba[:, :3] * gt_mask + bg * (1 - gt_mask)
-            out = model.render_stage1(rays_o, rays_d, self.mvps[v], self.H, self.W, bg_color=bg, shading=shading)
+            out = model.render_stage1(rays_o, rays_d, self.mvps[v], self.H, self.W, bg_color=bg, shading=shading,
+                                      index=v if self.capture is not None else None)
             loss = opt.lambda_rgb * F.mse_loss(out["image"], gt_rgb, reduction="none").mean(-1)
             if opt.lambda_mask > 0 and self._lambda_mask() > 0:
                 loss = loss + opt.lambda_mask * F.mse_loss(out["weights_sum"].view(-1), gt_mask.view(-1), reduction="none")

@@ -19,6 +19,8 @@
   load (capture.Capture.load_nerf: the train split, and the test split if PATH has one) -> stage 0 (step executor on the uint8 bank)
   -> export_stage0(dataset=capture, clean, decimate) -> stage 1 on that mesh (views from the capture) -> export_stage1(atlas="charts")
   -> one JSON line: held-out PSNR of both stages (the test split; without one, the training views) and evaluate_export of the written files.
+     `train_loss_tail` is the mean stage-0 training loss over the last 100 steps and `ind_dim` the code width (--ind_dim): two runs of the same
+     schedule and seed with --ind_dim 0 and 8 report what the per-image codes buy on a set whose exposure varies.
 
 Reads nothing but PATH; writes under --workspace.  With --bound > 1 stage 1 refines the inner mesh (cascade 0) only."""
 import argparse
@@ -60,6 +62,8 @@ ap.add_argument("--resolution", type=int, default=None, help="marching-cubes res
 ap.add_argument("--decimate_target", type=float, default=3e5)
 ap.add_argument("--texture", type=int, default=2048)
 ap.add_argument("--eval_views", type=int, default=8, help="held-out views the PSNRs are averaged over")
+ap.add_argument("--ind_dim", type=int, default=0, help="per-image appearance code width (0 = off); up to 16 runs the fused field kernels")
+ap.add_argument("--ind_num", type=int, default=500, help="code rows; at least the number of training views")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -112,17 +116,21 @@ opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 
                    offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace,
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
                    enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics,
-                   lambda_depth=args.lambda_depth)
+                   lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num)
 model = NeRFNetwork(opt)
 if colmap:
     model.to(dev)
     model.update_aabb(cap.pts_aabb.to(dev))              # main.py:234-235
-cls = Stage0Engine if Stage0Engine.supported(model, opt) else Stage0Trainer
+cls = Stage0Engine if Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
 eng = cls(model, opt, None, dev, seed=args.seed, capture=cap)
 eng.mark_untrained()
 t0 = time.perf_counter()
+tail0 = []                                   # the last training losses of stage 0 (device scalars): what two runs with and without --ind_dim compare
 for _ in range(args.iters0):
-    eng.train_step()
+    tail0.append(eng.train_step().detach().reshape(()).clone())
+    if len(tail0) > 100:
+        tail0.pop(0)
+train_loss_tail = float(torch.stack(tail0).mean()) if tail0 else float("nan")
 psnr0 = [eng.eval_psnr(cam=v, downscale=1, use_ema=True, capture=held) for v in views]
 clock("stage 0", t0, f"{args.iters0} steps ({cls.__name__}), held-out PSNR {np.mean(psnr0):.2f} dB")
 
@@ -161,7 +169,7 @@ clock("export_stage1", t0, "files: " + ", ".join(sorted(os.listdir(out_dir))))
 depth_steps = sum(v is not None for v in eng.depth_schedule.log[:args.iters0]) if getattr(eng, "depth_schedule", None) is not None else 0
 if args.enable_dense_depth:
     depth_steps = args.iters0                  # every step carries the depth term
-print(json.dumps({"data_format": args.data_format, "per_view_intrinsics": bool(cap.per_view_intrinsics), "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
+print(json.dumps({"data_format": args.data_format, "ind_dim": args.ind_dim, "train_loss_tail": train_loss_tail, "per_view_intrinsics": bool(cap.per_view_intrinsics), "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
                   "bank_mb": round(cap.nbytes / 1e6, 3), "iters0": args.iters0, "iters1": args.iters1, "faces": int(f0.shape[0]),
                   "psnr_stage0": float(np.mean(psnr0)), "psnr_stage1": float(np.mean(psnr1)), "export_psnr_vs_stage1": ev["mean"],
                   "export_psnr_per_view": ev["psnr_vs_stage1"]}))
