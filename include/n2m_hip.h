@@ -777,56 +777,41 @@ int n2m_get_rays(const float* poses, const int64_t* cam, const int64_t* pix, uin
                  float fx, float fy, float cx, float cy, const float* images, float* rays_o, float* rays_d,
                  float* rgba, void* stream);
 
-/* A whole training batch from ONE tensor of uniforms [N,6] in [0,1): view = floor(u0 V), pixel = floor(u1 H W) (random pixels over
- * random views, nerf/provider.py:302-303, nerf/utils.py:271), rays + ground truth as n2m_get_rays, near/far as n2m_near_far_from_aabb,
- * march jitter noises [N] = u2, random background bg [N,3] = u3..u5 (may be NULL), and *counter = 0 (may be NULL).  H*W < 2^24. */
-int n2m_batch_rays(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy, float cx,
-                   float cy, const float* images, const float* aabb, float min_near, float* rays_o, float* rays_d, float* rgba,
-                   float* nears, float* fars, float* noises, float* bg, int32_t* counter, void* stream);
-/* The same with the per-view near / far clamp of `--enable_cam_near_far` (nerf/renderer.py:689-691; colmap_provider.py:270,563-565 hands
- * every ray the (near, far) of its camera): cam_near_far [V,2] f32, nears = max(nears, cnf[view,0]), fars = min(fars, cnf[view,1]); NULL =
- * n2m_batch_rays. */
-int n2m_batch_rays_cnf(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy, float cx,
-                       float cy, const float* images, const float* aabb, float min_near, float* rays_o, float* rays_d, float* rgba,
-                       float* nears, float* fars, float* noises, float* bg, int32_t* counter, const float* cam_near_far, void* stream);
-
-/* Captured image sets (csrc/capture.hip, nerf2mesh_amd/capture.py).  bank: [V, H*W] packed RGBA8 words, R in the low byte (the reference's
- * uint8 image bank, nerf/provider.py:237; a 3-channel source stores alpha 255); lut: [2,256] f32 decode table built on the host (row 0: R, G,
- * B -- x / 255, or srgb_to_linear of it under --color_space linear, nerf/provider.py:323-325 --, row 1: alpha = x / 255).
- * n2m_batch_rays_u8: n2m_batch_rays_cnf with the ground truth gathered from the bank (same arithmetic, same operand order otherwise). */
-int n2m_batch_rays_u8(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy, float cx,
-                      float cy, const uint32_t* bank, const float* lut, const float* aabb, float min_near, float* rays_o, float* rays_d,
-                      float* rgba, float* nears, float* fars, float* noises, float* bg, int32_t* counter, const float* cam_near_far,
-                      void* stream);
-/* views_out [N] i32: the view each ray of the batch drawn from uniforms [N,6] reads -- column 0 through the SAME device function the three
- * batch kernels (n2m_batch_rays_u8, _u8_depth, _u8_pv) use.  Needed by the per-image appearance codes (--ind_dim, n2m_mlp.h) only; a
- * sparse-depth batch has one view, which the host knows. */
+/* A whole training batch from ONE tensor of uniforms [N,6] in [0,1), one launch (csrc/capture.hip): per ray the pixel, the ray + ground
+ * truth as n2m_get_rays, near/far as n2m_near_far_from_aabb, march jitter noises [N] = u2, random background bg [N,3] = u3..u5 and
+ * *counter = 0.  Zero / NULL in a field means "off".
+ *   the pixel         view = floor(u0 V), pixel = floor(u1 H W) (random pixels over random views, nerf/provider.py:302-303, nerf/utils.py:271).
+ *                     With `coords` set (sparse-depth supervision, nerf/colmap_provider.py:510-522) the batch is the keypoints of ONE view:
+ *                     coords [Ktot,2] i32 (row, col), kp_depth / kp_weight [Ktot] f32 are the whole CSR table of
+ *                     capture.Capture.sparse_depth, [first, first + N) the entries of `view`; ray n goes through the centre of pixel
+ *                     coords[first + n], columns 0, 1 of the uniforms are not read, and gt_depth [N], depth_weight [N] <- the keypoints'.
+ *                     Needs bank; takes the view's four scalar intrinsics, no table and no depth_bank.
+ *   the intrinsics    fx, fy, cx, cy, or -- intrinsics != NULL -- row v of intrinsics [V,4] f32 = (fx, fy, cx, cy), 16-byte aligned (per-view
+ *                     sets, capture.Capture.per_view_intrinsics; nerf/colmap_provider.py:521,540, nerf/dtu_provider.py:265).  The
+ *                     arithmetic is the same operand for operand: a table of equal rows gives the scalars' bits.
+ *   the ground truth  exactly one of images [V,H*W,4] f32 and bank [V,H*W] packed RGBA8 words, R in the low byte (the reference's uint8
+ *                     image bank, nerf/provider.py:237; a 3-channel source stores alpha 255) with lut [2,256] f32, the decode table built
+ *                     on the host (row 0: R, G, B -- x / 255, or srgb_to_linear of it under --color_space linear, nerf/provider.py:323-325
+ *                     --, row 1: alpha = x / 255).  Beside the bank, depth_bank [V,H*W] f32 (capture.Capture.dense_depth,
+ *                     --enable_dense_depth, nerf/colmap_provider.py:552-553) and gt_depth [N] are both set or both NULL (N2M_ENULL):
+ *                     gt_depth[n] <- depth_bank[view_n, pixel_n], one 4-byte gather at the index the colour word is read from.
+ *   the clamp         cam_near_far [V,2] f32 (`--enable_cam_near_far`, nerf/renderer.py:689-691; colmap_provider.py:270,563-565):
+ *                     nears = max(nears, cnf[view,0]), fars = min(fars, cnf[view,1]).
+ * V >= 1, 1 <= H*W < 2^24 (pixel index from an fp32 uniform), view < V, first + N < 2^31. */
+typedef struct {
+    const float* poses; const float* uniforms; uint32_t V, N, H, W;
+    float fx, fy, cx, cy; const float* intrinsics;
+    const float* images; const uint32_t* bank; const float* lut; const float* depth_bank;
+    const int32_t* coords; const float* kp_depth; const float* kp_weight; uint32_t view, first;
+    const float* aabb; float min_near; const float* cam_near_far;
+    float* rays_o; float* rays_d; float* rgba; float* nears; float* fars; float* noises; float* bg;   /* [N,3] x 2, [N,4], [N] x 3, [N,3] (may be NULL) */
+    float* gt_depth; float* depth_weight; int32_t* counter;
+} N2mBatchRays;   /* HOST struct */
+int n2m_batch_rays(const N2mBatchRays* d, void* stream);
+/* views_out [N] i32: the view each ray of the batch drawn from uniforms [N,6] reads -- column 0 through the SAME device function the
+ * batch kernel uses.  Needed by the per-image appearance codes (--ind_dim, n2m_mlp.h) only; a sparse-depth batch has one view, which the
+ * host knows. */
 int n2m_batch_views(const float* uniforms, uint32_t V, uint32_t N, int32_t* views_out, void* stream);
-/* n2m_batch_rays_u8 for the keypoints of ONE view (sparse-depth supervision, nerf/colmap_provider.py:510-522): coords [Ktot,2] i32 (row, col),
- * kp_depth / kp_weight [Ktot] f32 are the whole CSR table of capture.Capture.sparse_depth, [first, first + K) the entries of `view`.  Ray n goes
- * through the centre of pixel coords[first + n]; uniforms [K,6] supply the march jitter (column 2) and the background (3..5), columns 0, 1
- * are not read.  Writes what n2m_batch_rays_u8 writes per ray (the near / far clamp is cam_near_far[view]) + gt_depth [K], depth_weight [K]. */
-int n2m_batch_rays_sparse_u8(const float* poses, const float* uniforms, uint32_t V, uint32_t view, uint32_t first, uint32_t K, uint32_t H,
-                             uint32_t W, float fx, float fy, float cx, float cy, const uint32_t* bank, const float* lut, const float* aabb,
-                             float min_near, const int32_t* coords, const float* kp_depth, const float* kp_weight, float* rays_o, float* rays_d,
-                             float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth, float* depth_weight,
-                             int32_t* counter, const float* cam_near_far, void* stream);
-/* n2m_batch_rays_u8 + the dense-depth target of --enable_dense_depth (nerf/colmap_provider.py:552-553): depth_bank [V, H*W] f32
- * (capture.Capture.dense_depth), gt_depth [N] f32 <- depth_bank[view_n, pixel_n], one 4-byte gather at the index the colour word is read
- * from.  Every other output has n2m_batch_rays_u8's bits.  depth_bank or gt_depth NULL: N2M_ENULL. */
-int n2m_batch_rays_u8_depth(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
-                            float cx, float cy, const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb,
-                            float min_near, float* rays_o, float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg,
-                            float* gt_depth, int32_t* counter, const float* cam_near_far, void* stream);
-/* n2m_batch_rays_u8 / n2m_batch_rays_u8_depth for a set with PER-VIEW intrinsics (capture.Capture.per_view_intrinsics; the reference samples
- * intrinsics [N,4] per ray, nerf/colmap_provider.py:521,540, nerf/dtu_provider.py:265): intrinsics [V,4] f32 rows (fx, fy, cx, cy), 16-byte
- * aligned; ray n takes the row of the view it draws from u0.  depth_bank and gt_depth both NULL: the plain batch (seven outputs); both
- * set: gt_depth as n2m_batch_rays_u8_depth; exactly one of them NULL: N2M_ENULL.  Every output has n2m_batch_rays_u8's arithmetic, operand
- * for operand: a table of equal rows gives the bits of the shared-intrinsics entry points. */
-int n2m_batch_rays_u8_pv(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, const float* intrinsics,
-                         const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb, float min_near, float* rays_o,
-                         float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth, int32_t* counter,
-                         const float* cam_near_far, void* stream);
 /* One view of the dense-depth bank: dst [H*W] f32 = bilinear(src [h,w] f32) * scale + bias.  cv2.INTER_LINEAR's geometry: source
  * coordinate (x + 0.5) * rx - 0.5 and (y + 0.5) * ry - 0.5 with rx = w / W, ry = h / H rounded to fp32 by the caller, both taps of an axis
  * clamped to the edge, fp32 weights, a + (b - a) * t per axis (columns, then rows), multiply and add unfused: bit for bit
@@ -858,51 +843,43 @@ int n2m_photo_loss_backward(const float* image, const float* weights_sum, const 
                             const float* grad_loss, float* d_image, float* d_weights_sum, void* stream);
 
 /* Training fast path: n2m_composite_rays_train_forward -> n2m_photo_loss_forward -> n2m_photo_loss_backward ->
- * n2m_composite_rays_train_backward as ONE launch (density mode, the plain rgb + mask loss: no gradient into weights or depth;
- * n2m_composite_loss_train_ent adds the one into weights, n2m_composite_loss_train_depth the one into depth).
- * A wave composites its ray, forms the ray's loss term and gradients and runs the backward scan right away (the seed gradient
- * *grad_loss / N does not depend on the loss value).  grad_sigmas [M] / grad_rgbs [M,3] are bit-identical to the four-call chain
- * (every sample of a ray's range is written); weights_sum [N] and image [N,3] (colour before the background blend) may be NULL;
- * partial: ceil(N/16) floats scratch; ticket: one zero uint32 (left zero); loss [1] = the mean over rays; loss_sum (may be NULL) += loss.
- * ticket == NULL: the kernel only leaves the per-workgroup partials (no fence, no arrival atomics); n2m_scaler_update_slots_loss sums them. */
-int n2m_composite_loss_train(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                             float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb, float lambda_mask,
-                             const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas, float* grad_rgbs, float* partial,
-                             uint32_t* ticket, float* loss, float* loss_sum, void* stream);
-/* The same + the entropy regulariser of nerf/utils.py:728-733 (config 4: `--lambda_entropy 1e-3`, scripts/runall_360_outdoor.sh:2):
- * loss += lambda_entropy * (mean over the M samples of H(clamp(w)) + mean over the N rays of H(clamp(weights_sum))),
- * H(p) = -p log2 p - (1 - p) log2 (1 - p), clamp to [1e-5, 1 - 1e-5].  Its gradient w.r.t. a sample's weight is the `grad_weights` input of
- * composite_rays_train's backward and enters grad_sigmas exactly where the reference kernel reads grad_weights[i] (raymarching.cu:676).
- * lambda_entropy == 0: identical to n2m_composite_loss_train. */
-int n2m_composite_loss_train_ent(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                                 float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb, float lambda_mask,
-                                 const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas, float* grad_rgbs, float* partial,
-                                 uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy, void* stream);
-/* ... and with alpha_mode != 0 the SDF recipe's compositing (raymarching.cu:534,671: `sigmas` ARE the alphas, backward scale 1 / (1 - alpha);
- * nerf/renderer.py:739-741).  The entropy term is not available in alpha mode. */
-int n2m_composite_loss_train_ex(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                                float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb, float lambda_mask,
-                                const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas, float* grad_rgbs, float* partial,
-                                uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy, int alpha_mode, void* stream);
-/* n2m_composite_loss_train_ent + the sparse-depth term of nerf/utils.py:685-705 (density mode):
- *   loss_n += lambda_depth * depth_weight[n] * (depth_n * m - gt_depth[n] * m)^2,   m = (gt_depth[n] > 0),   depth_n = sum_k w_k t_k
- * before the mean over rays (the reference adds an [N,1] term to an [N] one; the mean of the [N,N] broadcast is that same mean).  Its derivative
- * w.r.t. depth_n is the `grad_depth` input of composite_rays_train's backward (raymarching.cu:676-678).  depth [N] (may be NULL) <- depth_n,
- * bit-identical to n2m_composite_rays_train_forward's; gt_depth NULL: no depth term; depth_weight NULL: 1.  With lambda_depth == 0 or
- * gt_depth == 0 everywhere the gradients and the loss are bit-identical to n2m_composite_loss_train_ent.  alpha_mode != 0: N2M_EUNSUPPORTED. */
-int n2m_composite_loss_train_depth(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                                   float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb, float lambda_mask,
-                                   const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas, float* grad_rgbs, float* partial,
-                                   uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy, float* depth, const float* gt_depth,
-                                   const float* depth_weight, float lambda_depth, int alpha_mode, void* stream);
+ * n2m_composite_rays_train_backward as ONE launch.  A wave composites its ray, forms the ray's loss term and gradients and runs the backward
+ * scan right away (the seed gradient *grad_loss / N does not depend on the loss value).  grad_sigmas [M] / grad_rgbs [M,3] are bit-identical
+ * to the four-call chain (every sample of a ray's range is written); weights_sum [N] and image [N,3] (colour before the background blend)
+ * may be NULL; partial: ceil(N/16) floats scratch; ticket: one zero uint32 (left zero); loss [1] = the mean over rays; loss_sum (may be
+ * NULL) += loss.  ticket == NULL: the kernel only leaves the per-workgroup partials (no fence, no arrival atomics); n2m_scaler_update_slots
+ * sums them.  A ticket without loss: N2M_ENULL.  The optional terms:
+ *   lambda_entropy > 0   the entropy regulariser of nerf/utils.py:728-733 (config 4: `--lambda_entropy 1e-3`, scripts/runall_360_outdoor.sh:2):
+ *       loss += lambda_entropy * (mean over the M samples of H(clamp(w)) + mean over the N rays of H(clamp(weights_sum))),
+ *       H(p) = -p log2 p - (1 - p) log2 (1 - p), clamp to [1e-5, 1 - 1e-5].  Its gradient w.r.t. a sample's weight is the `grad_weights`
+ *       input of composite_rays_train's backward and enters grad_sigmas exactly where the reference kernel reads grad_weights[i]
+ *       (raymarching.cu:676).  0: no gradient into the weights.
+ *   alpha_mode != 0      the SDF recipe's compositing (raymarching.cu:534,671: `sigmas` ARE the alphas, backward scale 1 / (1 - alpha);
+ *       nerf/renderer.py:739-741).  Neither the entropy nor the depth term is built in alpha mode: N2M_EUNSUPPORTED.
+ *   gt_depth != NULL     the sparse-depth term of nerf/utils.py:685-705:
+ *       loss_n += lambda_depth * depth_weight[n] * (depth_n * m - gt_depth[n] * m)^2,   m = (gt_depth[n] > 0),   depth_n = sum_k w_k t_k
+ *       before the mean over rays (the reference adds an [N,1] term to an [N] one; the mean of the [N,N] broadcast is that same mean).  Its
+ *       derivative w.r.t. depth_n is the `grad_depth` input of composite_rays_train's backward (raymarching.cu:676-678).  depth_weight
+ *       NULL: 1.  With lambda_depth == 0 or gt_depth == 0 everywhere the gradients and the loss are bit-identical to the call without it.
+ *       depth [N] (may be NULL; selects the same kernels as gt_depth) <- depth_n, bit-identical to n2m_composite_rays_train_forward's.
+ *   live, block_live     both or neither (live-first sample order for the table backward; no reference counterpart; raymarching.cu:553,640:
+ *       composite_rays_train stops a ray at T < T_thresh, every later sample of the ray gets weight 0 and gradient 0 -- about half of the
+ *       samples of a trained batch): live [N] <- per ray the number of samples up to and including the one the early stop fell on,
+ *       block_live [ceil(N/16)] <- their sums per 16 rays. */
+typedef struct {
+    const float* sigmas; const float* rgbs; const float* ts; const int32_t* rays; uint32_t M, N; float T_thresh;
+    const float* gt_rgba; const float* bg; float bg_scalar, lambda_rgb, lambda_mask; const float* grad_loss;
+    float* weights_sum; float* image; float* grad_sigmas; float* grad_rgbs;
+    float* partial; uint32_t* ticket; float* loss; float* loss_sum;
+    float lambda_entropy; int alpha_mode;
+    float* depth; const float* gt_depth; const float* depth_weight; float lambda_depth;
+    int32_t* live; uint32_t* block_live;
+} N2mCompositeLoss;   /* HOST struct */
+int n2m_composite_loss_train(const N2mCompositeLoss* d, void* stream);
 
-/* Live-first sample order for the table backward (no reference counterpart; raymarching.cu:553,640: composite_rays_train stops a ray at
- * T < T_thresh, every later sample of the ray gets weight 0 and gradient 0 -- about half of the samples of a trained batch).
- * n2m_composite_live_counts: optional outputs of the NEXT n2m_composite_loss_train* calls of this thread (sticky; clear with NULL, NULL):
- *   live [N] <- per ray the number of samples up to and including the one the early stop fell on, block_live [ceil(N/16)] <- their sums per 16 rays.
- * n2m_sample_order_live_first: perm [M] <- sample indices with every ray's live prefix first (ray order), then every ray's remaining samples.
+/* n2m_sample_order_live_first: perm [M] <- sample indices with every ray's live prefix first (ray order), then every ray's remaining samples
+ * (live / block_live as n2m_composite_loss_train leaves them).
  * n2m_grid_backward_sample_order (include below, gridencoder): the binned pair backward then visits the samples in that order. */
-int n2m_composite_live_counts(int32_t* live, uint32_t* block_live);
 int n2m_sample_order_live_first(const int32_t* rays, const int32_t* live, const uint32_t* block_live, uint32_t N, uint32_t M,
                                 uint32_t* perm, void* stream);
 /* Sticky, per thread; NULL clears it.  perm [B]: the i-th sample the next n2m_grid_encode_backward_binned_pair[_half|_tvt] calls visit.  The
@@ -921,7 +898,7 @@ int n2m_grid_backward_merge_levels(uint32_t levels);
  * main.py:221 / nerf/utils.py:506,1187-1190).  All tensors fp32 and 16-byte aligned, except grad which may be fp16
  * (grad_is_half) and half_shadow (fp16 copy of the updated parameter, or NULL).  Gradients are still multiplied by *scale
  * (NULL = 1); no parameter or moment is touched when *found_inf != 0; bias [2] = (1 - beta1^t, sqrt(1 - beta2^t)) of this step, kept up to
- * date by n2m_scaler_update (initialise it to (1 - beta1, sqrt(1 - beta2)) for t = 1). */
+ * date by n2m_scaler_update_slots (initialise it to (1 - beta1, sqrt(1 - beta2)) for t = 1). */
 #define N2M_ADAM_MAX 16
 typedef struct {
     void* param[N2M_ADAM_MAX]; const void* grad[N2M_ADAM_MAX]; void* exp_avg[N2M_ADAM_MAX]; void* exp_avg_sq[N2M_ADAM_MAX];
@@ -951,42 +928,18 @@ typedef struct {
 } N2mEmaDesc;   /* HOST struct */
 int n2m_ema_update(const N2mEmaDesc* desc, float one_minus_decay, void* stream);
 
-/* GradScaler.update() on device scalars (floats): found_inf != 0 -> scale *= backoff, tracker = 0; else step += 1,
- * tracker += 1 and scale *= growth every growth_interval good steps; found_inf is reset to 0 and bias [2] recomputed (in
- * double) for the next step.  scale / growth_tracker / step / bias may be NULL. */
-int n2m_scaler_update(float* scale, float* growth_tracker, float* found_inf, float* step, float* bias, double beta1,
-                      double beta2, float growth_factor, float backoff_factor, float growth_interval, void* stream);
-/* The same with one step count per tensor slot, as torch.optim.Adam counts (state[p]["step"]: a parameter that receives its first
- * gradient late starts its bias corrections at t = 1).  steps [1 + N2M_ADAM_MAX] and bias [1 + N2M_ADAM_MAX][2], slot 0 = the
- * global count; participants: bit s-1 set = slot s took part in this step.  Initialise every bias row to (1-beta1, sqrt(1-beta2)). */
-int n2m_scaler_update_slots(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                            uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                            float growth_interval, void* stream);
-
-/* n2m_scaler_update_slots + loss = sum(loss_partial[0 .. n_partial)) / n_rays, *loss_sum += loss (either may be NULL). */
-int n2m_scaler_update_slots_loss(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                 uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                 float growth_interval, const float* loss_partial, uint32_t n_partial, uint32_t n_rays, float* loss,
-                                 float* loss_sum, void* stream);
-/* The same + a second term with its own normalisation: loss += extra_scale * sum(extra_partial[0 .. n_extra)).  The training step's
- * specular regulariser lambda_specular * mean_m sum_c specular^2 (nerf/utils.py:733-737) arrives this way: extra_partial = the
- * per-workgroup sums n2m_field_forward_train leaves, extra_scale = lambda_specular / M.  extra_partial == NULL: no second term. */
-int n2m_scaler_update_slots_loss2(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                  uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                  float growth_interval, const float* loss_partial, uint32_t n_partial, uint32_t n_rays, float* loss,
-                                  float* loss_sum, const float* extra_partial, uint32_t n_extra, float extra_scale, void* stream);
-/* ... and a third term, loss += extra2_scale * sum(extra2_partial[0 .. n_extra2)) (SDF recipe: the eikonal loss from n2m_sdf_alpha_forward's partials). */
-int n2m_scaler_update_slots_loss3(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                  uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                  float growth_interval, const float* loss_partial, uint32_t n_partial, uint32_t n_rays, float* loss,
-                                  float* loss_sum, const float* extra_partial, uint32_t n_extra, float extra_scale,
-                                  const float* extra2_partial, uint32_t n_extra2, float extra2_scale, void* stream);
-
-/* n2m_adam_step + n2m_scaler_update_slots_loss3 in ONE launch (round 6): the optimizer pass whose last workgroup to finish also does the
- * GradScaler / per-slot step count / bias-correction / loss-value bookkeeping (GradScaler.update of nerf/utils.py:1176-1177 behind
- * optimizer.step; main.py:221's torch.optim.Adam semantics as n2m_adam_step) -- the same code on the same 256 threads, bit-identical state and
- * loss value; scale / found_inf / bias are the arrays n2m_adam_step reads (here also written: the next step's values).  `ticket`: N2M_TAIL_TICKET_WORDS
- * uint32 of device memory (64 arrival counters, one 128-byte line each), zero before the first call; the launch leaves them zero.  One launch less on the step's critical path. */
+/* GradScaler.update() on device scalars (floats) + the step counts: found_inf != 0 -> scale *= backoff, tracker = 0; else the counts
+ * advance, tracker += 1 and scale *= growth every growth_interval good steps; found_inf is reset to 0 and the bias corrections recomputed (in
+ * double) for the next step.  scale / growth_tracker may be NULL.  One step count per tensor slot, as torch.optim.Adam counts
+ * (state[p]["step"]: a parameter that receives its first gradient late starts its bias corrections at t = 1): steps [1 + N2M_ADAM_MAX] and
+ * bias [1 + N2M_ADAM_MAX][2], slot 0 = the global count; participants: bit s-1 set = slot s took part in this step.  Initialise every
+ * bias row to (1-beta1, sqrt(1-beta2)).
+ * loss_partial != NULL: + the step's loss VALUE, loss = sum(loss_partial[0 .. n_partial)) / n_rays, *loss_sum += loss (either may be NULL),
+ * from the per-workgroup partials n2m_composite_loss_train leaves when it is given no ticket; n_rays == 0: N2M_EINVAL.  A second term with
+ * its own normalisation, loss += extra_scale * sum(extra_partial[0 .. n_extra)): the training step's specular regulariser
+ * lambda_specular * mean_m sum_c specular^2 (nerf/utils.py:733-737) arrives this way, extra_partial = the per-workgroup sums
+ * n2m_field_forward_train leaves, extra_scale = lambda_specular / M.  A third, extra2_* (SDF recipe: the eikonal loss from
+ * n2m_sdf_alpha_forward's partials).  `ticket` is n2m_adam_step_scaler's alone. */
 #define N2M_TAIL_TICKET_WORDS (64 * 32)
 typedef struct {
     float* growth_tracker; float* steps;
@@ -996,6 +949,14 @@ typedef struct {
     const float* extra2_partial; uint32_t n_extra2; float extra2_scale;        /* NULL: no third term */
     uint32_t* ticket;
 } N2mScalerTail;   /* HOST struct */
+int n2m_scaler_update_slots(float* scale, float* found_inf, float* bias, double beta1, double beta2, const N2mScalerTail* tail, void* stream);
+
+/* n2m_adam_step + n2m_scaler_update_slots in ONE launch (round 6): the optimizer pass whose last workgroup to finish also does the
+ * GradScaler / per-slot step count / bias-correction / loss-value bookkeeping (GradScaler.update of nerf/utils.py:1176-1177 behind
+ * optimizer.step; main.py:221's torch.optim.Adam semantics as n2m_adam_step) -- the same code on the same 256 threads, bit-identical state and
+ * loss value; scale / found_inf / bias are the arrays n2m_adam_step reads (here also written: the next step's values).  `ticket`: N2M_TAIL_TICKET_WORDS
+ * uint32 of device memory (64 arrival counters, one 128-byte line each), zero before the first call; the launch leaves them zero.  Needs the
+ * loss partials.  One launch less on the step's critical path. */
 int n2m_adam_step_scaler(const N2mAdamDesc* desc, double beta1, double beta2, float eps, float* scale, float* found_inf, float* bias,
                          const N2mScalerTail* tail, void* stream);
 

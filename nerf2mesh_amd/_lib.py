@@ -28,7 +28,6 @@ SIGNATURES = {
     "n2m_march_fallback_count": [_vp],
     "n2m_debug_fill_times": [_int, _vp],
     "n2m_stream_copy": [_vp, _vp, _u64, _u32, _vp],
-    "n2m_composite_live_counts": [_vp, _vp],
     "n2m_sample_order_live_first": [_vp, _vp, _vp, _u32, _u32, _vp, _vp],
     "n2m_grid_backward_sample_order": [_vp],
     "n2m_grid_backward_config": [_int, _f32],
@@ -36,11 +35,7 @@ SIGNATURES = {
     "n2m_grid_backward_mid_event": [_vp],
     "n2m_composite_rays_train_forward": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _int, _vp, _vp, _vp, _vp, _vp],
     "n2m_composite_rays_train_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _int, _vp, _vp, _vp],
-    "n2m_composite_loss_train": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "n2m_composite_loss_train_ent": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp],
-    "n2m_composite_loss_train_depth": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32,
-                                       _vp, _vp, _vp, _f32, _int, _vp],
-    "n2m_composite_loss_train_ex": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _int, _vp],
+    "n2m_composite_loss_train": [_vp, _vp],
     "n2m_march_rays": [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _int, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_composite_rays": [_u32, _u32, _f32, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_compact_alive": [_vp, _u32, _vp, _vp, _vp],
@@ -135,28 +130,15 @@ SIGNATURES = {
     "n2m_freq_encode_forward": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_get_rays": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
-    "n2m_batch_rays": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "n2m_batch_rays_cnf": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "n2m_batch_rays_u8": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "n2m_batch_rays": [_vp, _vp],
     "n2m_batch_views": [_vp, _u32, _u32, _vp, _vp],
-    "n2m_batch_rays_sparse_u8": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "n2m_batch_rays_u8_depth": [_vp, _vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                _vp, _vp, _vp, _vp],
-    "n2m_batch_rays_u8_pv": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_depth_bank_fill": [_vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
     "n2m_capture_view": [_vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "n2m_capture_box_downscale": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_adam_step": [_vp, ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp],
     "n2m_adam_step_scaler": [_vp, ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp, _vp],
     "n2m_ema_update": [_vp, _f32, _vp],
-    "n2m_scaler_update": [_vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _f32, _f32, _f32, _vp],
-    "n2m_scaler_update_slots": [_vp, _vp, _vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _f32, _f32, _f32, _vp],
-    "n2m_scaler_update_slots_loss": [_vp, _vp, _vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _f32, _f32, _f32, _vp, _u32, _u32, _vp, _vp, _vp],
-    "n2m_scaler_update_slots_loss2": [_vp, _vp, _vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _f32, _f32, _f32, _vp, _u32, _u32, _vp, _vp,
-                                      _vp, _u32, _f32, _vp],
-    "n2m_scaler_update_slots_loss3": [_vp, _vp, _vp, _vp, _vp, _u32, ctypes.c_double, ctypes.c_double, _f32, _f32, _f32, _vp, _u32, _u32, _vp, _vp,
-                                      _vp, _u32, _f32, _vp, _u32, _f32, _vp],
+    "n2m_scaler_update_slots": [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp],
     "n2m_sdf_offsets": [_vp, _u32, _f32, _f32, _vp, _vp, _vp],
     "n2m_sdf_alpha_forward": [_vp, _vp, _vp, _vp, _u32, _vp, _f32, _f32, _vp, _vp, _vp, _vp],
     "n2m_sdf_alpha_backward": [_vp, _vp, _vp, _vp, _vp, _u32, _vp, _f32, _f32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
@@ -239,6 +221,24 @@ class ScalerTail(ctypes.Structure):
                 ("growth_interval", _f32), ("loss_partial", _vp), ("n_partial", _u32), ("n_rays", _u32), ("loss", _vp), ("loss_sum", _vp),
                 ("extra_partial", _vp), ("n_extra", _u32), ("extra_scale", _f32), ("extra2_partial", _vp), ("n_extra2", _u32),
                 ("extra2_scale", _f32), ("ticket", _vp)]
+
+
+class BatchRays(ctypes.Structure):
+    """N2mBatchRays of include/n2m_hip.h."""
+    _fields_ = [("poses", _vp), ("uniforms", _vp), ("V", _u32), ("N", _u32), ("H", _u32), ("W", _u32), ("fx", _f32), ("fy", _f32), ("cx", _f32),
+                ("cy", _f32), ("intrinsics", _vp), ("images", _vp), ("bank", _vp), ("lut", _vp), ("depth_bank", _vp), ("coords", _vp),
+                ("kp_depth", _vp), ("kp_weight", _vp), ("view", _u32), ("first", _u32), ("aabb", _vp), ("min_near", _f32), ("cam_near_far", _vp),
+                ("rays_o", _vp), ("rays_d", _vp), ("rgba", _vp), ("nears", _vp), ("fars", _vp), ("noises", _vp), ("bg", _vp), ("gt_depth", _vp),
+                ("depth_weight", _vp), ("counter", _vp)]
+
+
+class CompositeLoss(ctypes.Structure):
+    """N2mCompositeLoss of include/n2m_hip.h."""
+    _fields_ = [("sigmas", _vp), ("rgbs", _vp), ("ts", _vp), ("rays", _vp), ("M", _u32), ("N", _u32), ("T_thresh", _f32), ("gt_rgba", _vp),
+                ("bg", _vp), ("bg_scalar", _f32), ("lambda_rgb", _f32), ("lambda_mask", _f32), ("grad_loss", _vp), ("weights_sum", _vp),
+                ("image", _vp), ("grad_sigmas", _vp), ("grad_rgbs", _vp), ("partial", _vp), ("ticket", _vp), ("loss", _vp), ("loss_sum", _vp),
+                ("lambda_entropy", _f32), ("alpha_mode", _int), ("depth", _vp), ("gt_depth", _vp), ("depth_weight", _vp), ("lambda_depth", _f32),
+                ("live", _vp), ("block_live", _vp)]
 
 
 EMA_MAX = 16

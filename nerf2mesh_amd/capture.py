@@ -15,6 +15,7 @@ nerf/colmap_provider.py:165-182, 521, 540; nerf/dtu_provider.py:93-104, 265); H 
 are allowed.  `mvps` is built FROM those intrinsics (proj_matrix), so the rasteriser of stage 1 and the rays of stage 0 see the same
 camera; the reference's projection (nerf/provider.py:266-276) ignores cx, cy and fl_x, so off-centre its rays and its raster disagree.
 """
+import ctypes
 import json
 import math
 import os
@@ -107,11 +108,11 @@ def intrinsics_row(intrinsics, view):
 
 def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None, dense_depth=None):
     """synthetic.batch_from_uniforms with the ground truth gathered from a packed uint8 bank [V,H*W] and decoded through `lut`.  On the GPU
-    one kernel (n2m_batch_rays_u8); below it the torch statement of the same arithmetic, taken on the CPU.  dense_depth [V,H*W] fp32
-    (Capture.dense_depth, --enable_dense_depth): an eighth tensor gt_depth [N] = dense_depth[view_n, pixel_n] follows the seven (`out`
-    then has eight entries); on the GPU n2m_batch_rays_u8_depth.  intrinsics: (fx, fy, cx, cy), or the table form of a per-view set
-    (Capture.intrinsics, fp32 [V,4] beside the poses): ray n takes the row of its view -- on the GPU n2m_batch_rays_u8_pv, with or without
-    a depth bank; on the CPU the same statement with the rows gathered at `cam`."""
+    one kernel (n2m_batch_rays, every form below one descriptor); below it the torch statement of the same arithmetic, taken on the CPU.
+    dense_depth [V,H*W] fp32 (Capture.dense_depth, --enable_dense_depth): an eighth tensor gt_depth [N] = dense_depth[view_n, pixel_n]
+    follows the seven (`out` then has eight entries).  intrinsics: (fx, fy, cx, cy), or the table form of a per-view set
+    (Capture.intrinsics, fp32 [V,4] beside the poses): ray n takes the row of its view, with or without a depth bank; on the CPU the same
+    statement with the rows gathered at `cam`."""
     dev = poses.device
     N, V = u.shape[0], poses.shape[0]
     table = intrinsics_table(intrinsics, V, dev)
@@ -119,51 +120,26 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
         fx, fy, cx, cy = (float(x) for x in intrinsics)
     if dense_depth is not None and tuple(dense_depth.shape) != tuple(bank.shape):
         raise ValueError(f"the depth bank is {tuple(dense_depth.shape)}, the image bank {tuple(bank.shape)}")
-    if dev.type == "cuda" and table is not None:
-        from . import _lib as L
-        n_out = 7 if dense_depth is None else 8
-        if out is None:
-            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            out = (f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3)) + (() if dense_depth is None else (f(N),))
-        o, d, rgba, nears, fars, noises, bg = out[:7]
-        gtd = out[7] if n_out == 8 else None
-        L.call("n2m_batch_rays_u8_pv", L.ptr(poses), L.ptr(u), V, N, H, W, L.ptr(table), L.ptr(bank), L.ptr(dense_depth), L.ptr(lut), L.ptr(aabb),
-               float(min_near), L.ptr(o), L.ptr(d), L.ptr(rgba), L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(gtd), L.ptr(counter),
-               L.ptr(cam_near_far), L.stream())
-        return (o, d, rgba, nears, fars, noises, bg) + (() if gtd is None else (gtd,))
-    if dev.type == "cuda" and dense_depth is not None:
-        from . import _lib as L
-        if out is None:
-            f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            out = (f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3), f(N))
-        o, d, rgba, nears, fars, noises, bg, gtd = out
-        L.call("n2m_batch_rays_u8_depth", L.ptr(poses), L.ptr(u), V, N, H, W, fx, fy, cx, cy, L.ptr(bank), L.ptr(dense_depth), L.ptr(lut), L.ptr(aabb),
-               float(min_near), L.ptr(o), L.ptr(d), L.ptr(rgba), L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(gtd), L.ptr(counter),
-               L.ptr(cam_near_far), L.stream())
-        return o, d, rgba, nears, fars, noises, bg, gtd
     if dev.type == "cuda":
         from . import _lib as L
         if out is None:
             f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
-            out = (f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3))
-        o, d, rgba, nears, fars, noises, bg = out
-        L.call("n2m_batch_rays_u8", L.ptr(poses), L.ptr(u), V, N, H, W, fx, fy, cx, cy, L.ptr(bank), L.ptr(lut), L.ptr(aabb), float(min_near),
-               L.ptr(o), L.ptr(d), L.ptr(rgba), L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(counter), L.ptr(cam_near_far), L.stream())
-        return o, d, rgba, nears, fars, noises, bg
+            out = (f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3)) + (() if dense_depth is None else (f(N),))
+        o, d, rgba, nears, fars, noises, bg = out[:7]
+        gtd = None if dense_depth is None else out[7]
+        desc = L.BatchRays(poses=L.ptr(poses), uniforms=L.ptr(u), V=V, N=N, H=H, W=W, intrinsics=L.ptr(table), bank=L.ptr(bank), lut=L.ptr(lut),
+                           depth_bank=L.ptr(dense_depth), aabb=L.ptr(aabb), min_near=float(min_near), cam_near_far=L.ptr(cam_near_far),
+                           rays_o=L.ptr(o), rays_d=L.ptr(d), rgba=L.ptr(rgba), nears=L.ptr(nears), fars=L.ptr(fars), noises=L.ptr(noises),
+                           bg=L.ptr(bg), gt_depth=L.ptr(gtd), counter=L.ptr(counter))
+        if table is None:
+            desc.fx, desc.fy, desc.cx, desc.cy = fx, fy, cx, cy
+        L.call("n2m_batch_rays", ctypes.addressof(desc), L.stream())
+        return (o, d, rgba, nears, fars, noises, bg) + (() if gtd is None else (gtd,))
     cam = (u[:, 0] * V).long().clamp(max=V - 1)
     pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
     o, d = rays_from_pixels(poses, cam, pix % W, torch.div(pix, W, rounding_mode="floor"),
                             (fx, fy, cx, cy) if table is None else table[cam].unbind(-1))
-    inv = 1.0 / d
-    lo, hi = (aabb[:3] - o) * inv, (aabb[3:] - o) * inv
-    tn, tf = torch.minimum(lo, hi).amax(-1), torch.maximum(lo, hi).amin(-1)
-    miss = tn > tf
-    big = torch.finfo(torch.float32).max
-    nears = torch.where(miss, torch.full_like(tn, big), tn.clamp(min=min_near))
-    fars = torch.where(miss, torch.full_like(tf, big), tf)
-    if cam_near_far is not None:
-        nears = torch.maximum(nears, cam_near_far[cam, 0])
-        fars = torch.minimum(fars, cam_near_far[cam, 1])
+    nears, fars = synthetic.near_far_clamped(o, d, aabb, min_near, cam_near_far, cam)
     if counter is not None:
         counter.zero_()
     seven = (o, d, decode_words(bank[cam, pix], lut), nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous())
@@ -191,7 +167,7 @@ def batch_views(u, V, out=None):
 def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None):
     """The depth-bearing batch of ONE view (nerf/colmap_provider.py:510-522): a ray through the centre of every keypoint of `view` in the
     CSR table `sparse_depth` (SparseDepth), jitter and background from u [K_v,6] (columns 2 and 3..5).  Returns batch_from_uniforms_u8's
-    seven tensors + gt_depth [K_v], depth_weight [K_v].  On the GPU one kernel (n2m_batch_rays_sparse_u8); below it the torch statement."""
+    seven tensors + gt_depth [K_v], depth_weight [K_v].  On the GPU one kernel (n2m_batch_rays in keypoint mode); below it the torch statement."""
     dev = poses.device
     V, v = poses.shape[0], int(view)
     first, K = sparse_depth.range(v)
@@ -204,23 +180,17 @@ def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, 
             f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             out = (f(K, 3), f(K, 3), f(K, 4), f(K), f(K), f(K), f(K, 3), f(K), f(K))
         o, d, rgba, nears, fars, noises, bg, gtd, dw = out
-        L.call("n2m_batch_rays_sparse_u8", L.ptr(poses), L.ptr(u), V, v, first, K, H, W, fx, fy, cx, cy, L.ptr(bank), L.ptr(lut), L.ptr(aabb),
-               float(min_near), L.ptr(sparse_depth.coords), L.ptr(sparse_depth.depth), L.ptr(sparse_depth.weight), L.ptr(o), L.ptr(d), L.ptr(rgba),
-               L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(gtd), L.ptr(dw), L.ptr(counter), L.ptr(cam_near_far), L.stream())
+        desc = L.BatchRays(poses=L.ptr(poses), uniforms=L.ptr(u), V=V, N=K, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, bank=L.ptr(bank), lut=L.ptr(lut),
+                           coords=L.ptr(sparse_depth.coords), kp_depth=L.ptr(sparse_depth.depth), kp_weight=L.ptr(sparse_depth.weight), view=v,
+                           first=first, aabb=L.ptr(aabb), min_near=float(min_near), cam_near_far=L.ptr(cam_near_far), rays_o=L.ptr(o),
+                           rays_d=L.ptr(d), rgba=L.ptr(rgba), nears=L.ptr(nears), fars=L.ptr(fars), noises=L.ptr(noises), bg=L.ptr(bg),
+                           gt_depth=L.ptr(gtd), depth_weight=L.ptr(dw), counter=L.ptr(counter))
+        L.call("n2m_batch_rays", ctypes.addressof(desc), L.stream())
         return o, d, rgba, nears, fars, noises, bg, gtd, dw
     rc = sparse_depth.coords[first:first + K].long()
     row, col = rc[:, 0].clamp(0, H - 1), rc[:, 1].clamp(0, W - 1)
     o, d = rays_from_pixels(poses, torch.full_like(row, v), col, row, (fx, fy, cx, cy))
-    inv = 1.0 / d
-    lo, hi = (aabb[:3] - o) * inv, (aabb[3:] - o) * inv
-    tn, tf = torch.minimum(lo, hi).amax(-1), torch.maximum(lo, hi).amin(-1)
-    miss = tn > tf
-    big = torch.finfo(torch.float32).max
-    nears = torch.where(miss, torch.full_like(tn, big), tn.clamp(min=min_near))
-    fars = torch.where(miss, torch.full_like(tf, big), tf)
-    if cam_near_far is not None:
-        nears = torch.maximum(nears, cam_near_far[v, 0])
-        fars = torch.minimum(fars, cam_near_far[v, 1])
+    nears, fars = synthetic.near_far_clamped(o, d, aabb, min_near, cam_near_far, v)
     if counter is not None:
         counter.zero_()
     return (o, d, decode_words(bank[v][row * W + col], lut), nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous(),

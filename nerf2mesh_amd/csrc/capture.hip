@@ -2,8 +2,8 @@
 // at gather time and converts sRGB -> linear under --color_space linear (nerf/provider.py:237,323-325; nerf/utils.py:640).  Here the bank is
 // one packed RGBA8 word per pixel (R in the low byte; a 3-channel source stores alpha 255) and the decode is a gather from a [2,256] fp32
 // table the host built with the reference's own torch expressions (row 0: R, G, B; row 1: alpha), so a decoded value has the bits of the
-// torch statement by construction -- no device pow.  Ray arithmetic is batch_rays_kernel's (raymarching.hip), operand for operand; this
-// file is compiled with -ffp-contract=off like the rest.
+// torch statement by construction -- no device pow.  The batch kernel of the synthetic (fp32) bank lives here too; this file is compiled
+// with -ffp-contract=off like the rest.
 #include "n2m_common.hpp"
 
 namespace {
@@ -22,167 +22,95 @@ __global__ void __launch_bounds__(256) batch_views_kernel(const float* __restric
     if (n < N) views_out[n] = (int32_t)view_of_uniform(u[(size_t)n * 6], V);
 }
 
-// batch_rays_kernel with the ground truth read from the packed bank: one 4-byte load per ray instead of a 16-byte one
-__global__ void __launch_bounds__(256)
-batch_rays_u8_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, uint32_t W,
-                     uint32_t HW, float fx, float fy, float cx, float cy, const uint32_t* __restrict__ bank /*[V,HW]*/,
-                     const float* __restrict__ lut /*[2,256]*/, const float* __restrict__ aabb, float min_near, float* __restrict__ rays_o,
-                     float* __restrict__ rays_d, float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars,
-                     float* __restrict__ noises, float* __restrict__ bg, int32_t* __restrict__ counter,
-                     const float* __restrict__ cam_near_far /*[V,2] or NULL*/) {
-    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0 && counter) counter[0] = 0;
-    if (n >= N) return;
-    const float* __restrict__ un = u + (size_t)n * 6;
-    const uint32_t v = view_of_uniform(un[0], V), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
-    const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
-    const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
-    const float* __restrict__ P = poses + (size_t)v * 16;
-    float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
-        o[k] = P[4 * k + 3];
-        rays_d[(size_t)n * 3 + k] = d[k];
-        rays_o[(size_t)n * 3 + k] = o[k];
-    }
-    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = decode_rgba8(bank[(size_t)v * HW + (size_t)p], lut);
-    float tn, tf;
-    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
-    if (cam_near_far) {
-        tn = fmaxf(tn, cam_near_far[2 * v]);
-        tf = fminf(tf, cam_near_far[2 * v + 1]);
-    }
-    nears[n] = tn; fars[n] = tf;
-    noises[n] = un[2];
-    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
-}
+// A whole training batch in one launch: per ray the pixel choice, the ray (exactly as n2m_get_rays builds it, nerf/utils.py:242-290), the
+// ground truth, near / far exactly as n2m_near_far_from_aabb + the per-view clamp of --enable_cam_near_far (nerf/renderer.py:689-691,
+// colmap_provider.py:563-565: maximum / minimum), the march jitter u2 and the random background u3..u5 (nerf/utils.py:649-652); also clears
+// the marcher's sample counter.  Seven small launches of the step's side stream are one (they ran 7-13 us EACH beside the optimizer update
+// and delayed the march behind them).  The three things a batch can differ in:
+//   the pixel         uniform mode: view = floor(u0 V), pixel = floor(u1 H W) (random_image_batch, nerf/provider.py:302-303);
+//                     KP (sparse-depth supervision, nerf/colmap_provider.py:510-522): pixel coords[n] = (row, col) of the ONE view `view`,
+//                     whose keypoint depth and weight are copied into the batch; columns 0, 1 of the uniforms are not read
+//   the intrinsics    four scalars, or row v of a [V,4] table (per-view sets, colmap_provider.py:521,540, dtu_provider.py:265): one 16-byte
+//                     load at the view index the ray already has; equal rows give the scalars' bits
+//   the ground truth  U8: the packed bank through the LUT (one 4-byte load) + the optional depth gather of --enable_dense_depth
+//                     (colmap_provider.py:552-553) at the same index; otherwise the fp32 images (one 16-byte load, nerf/provider.py:330)
+// The struct carries no __restrict__, so every load of a ray is written in front of its first store.
+struct BatchRaysK {
+    const float* poses; const float* u; uint32_t V, N, H, W, HW; float fx, fy, cx, cy; const float4* intrinsics;
+    const float* images; const uint32_t* bank; const float* lut; const float* depth_bank;
+    const int32_t* coords; const float* kp_depth; const float* kp_weight; uint32_t view;
+    const float* aabb; float min_near; const float* cam_near_far;
+    float* rays_o; float* rays_d; float* rgba; float* nears; float* fars; float* noises; float* bg; float* gt_depth; float* depth_weight;
+    int32_t* counter;
+};
 
-// batch_rays_u8_kernel for the keypoints of ONE view (sparse-depth supervision, nerf/colmap_provider.py:510-522): ray n goes through the
-// centre of pixel coords[n] = (row, col) of that view instead of a pixel drawn from the uniforms; jitter and background still come from
-// uniforms [K,6] (columns 2 and 3..5; columns 0, 1 are not read).  Also copies the keypoints' depth and weight into the batch.
-__global__ void __launch_bounds__(256)
-batch_rays_sparse_u8_kernel(const float* __restrict__ P /*[4,4] of the view*/, const float* __restrict__ u /*[K,6]*/, uint32_t K, uint32_t H,
-                            uint32_t W, float fx, float fy, float cx, float cy, const uint32_t* __restrict__ bank /*[H W] of the view*/,
-                            const float* __restrict__ lut /*[2,256]*/, const float* __restrict__ aabb, float min_near,
-                            const int32_t* __restrict__ coords /*[K,2]*/, const float* __restrict__ kp_depth /*[K]*/,
-                            const float* __restrict__ kp_weight /*[K]*/, float* __restrict__ rays_o, float* __restrict__ rays_d,
-                            float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ noises,
-                            float* __restrict__ bg, float* __restrict__ gt_depth, float* __restrict__ depth_weight,
-                            int32_t* __restrict__ counter, const float* __restrict__ near_far /*[2] of the view or NULL*/) {
-    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0 && counter) counter[0] = 0;
-    if (n >= K) return;
-    const float* __restrict__ un = u + (size_t)n * 6;
-    // (row, col) clamped to the image: the loader clips them already, the clamp keeps a hand-made table inside the bank
-    const uint32_t row = (uint32_t)min(max(coords[(size_t)n * 2], 0), (int32_t)H - 1);
-    const uint32_t col = (uint32_t)min(max(coords[(size_t)n * 2 + 1], 0), (int32_t)W - 1);
+// ray n through the centre of pixel (row, col) of view v: everything the three modes share
+template <bool U8>
+__device__ __forceinline__ void batch_ray(const BatchRaysK& k, uint32_t n, uint32_t v, uint32_t col, uint32_t row, float fx, float fy, float cx,
+                                          float cy) {
+    const float* un = k.u + (size_t)n * 6;
+    const float u2 = un[2], u3 = un[3], u4 = un[4], u5 = un[5];
+    const float box[6] = {k.aabb[0], k.aabb[1], k.aabb[2], k.aabb[3], k.aabb[4], k.aabb[5]};
     const float i = (float)col + 0.5f, j = (float)row + 0.5f;
     const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
+    const float* P = k.poses + (size_t)v * 16;
     float o[3], d[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
-        o[k] = P[4 * k + 3];
-        rays_d[(size_t)n * 3 + k] = d[k];
-        rays_o[(size_t)n * 3 + k] = o[k];
+    for (int c = 0; c < 3; ++c) {
+        d[c] = (d0 * P[4 * c] + d1 * P[4 * c + 1]) + d2 * P[4 * c + 2];
+        o[c] = P[4 * c + 3];
     }
-    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = decode_rgba8(bank[(size_t)row * W + (size_t)col], lut);
+    const size_t at = (size_t)v * k.HW + ((size_t)row * k.W + col);
+    float4 gt;
+    float gtd = 0.0f;
+    if constexpr (U8) {
+        gt = decode_rgba8(k.bank[at], k.lut);
+        if (k.depth_bank) gtd = k.depth_bank[at];
+    } else {
+        gt = *reinterpret_cast<const float4*>(k.images + at * 4);
+    }
     float tn, tf;
-    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
-    if (near_far) {
-        tn = fmaxf(tn, near_far[0]);
-        tf = fminf(tf, near_far[1]);
+    n2m_near_far_of(o, d, box, k.min_near, tn, tf);
+    if (k.cam_near_far) {
+        tn = fmaxf(tn, k.cam_near_far[2 * v]);
+        tf = fminf(tf, k.cam_near_far[2 * v + 1]);
     }
-    nears[n] = tn; fars[n] = tf;
-    noises[n] = un[2];
-    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
-    gt_depth[n] = kp_depth[n];
-    depth_weight[n] = kp_weight[n];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        k.rays_d[(size_t)n * 3 + c] = d[c];
+        k.rays_o[(size_t)n * 3 + c] = o[c];
+    }
+    *reinterpret_cast<float4*>(k.rgba + (size_t)n * 4) = gt;
+    if constexpr (U8)
+        if (k.depth_bank) k.gt_depth[n] = gtd;
+    k.nears[n] = tn; k.fars[n] = tf;
+    k.noises[n] = u2;
+    if (k.bg) { k.bg[(size_t)n * 3] = u3; k.bg[(size_t)n * 3 + 1] = u4; k.bg[(size_t)n * 3 + 2] = u5; }
 }
 
-// batch_rays_u8_kernel + the dense-depth target of --enable_dense_depth (nerf/colmap_provider.py:552-553): gt_depth[n] is gathered from the
-// fp32 depth bank [V,HW] at the index the colour word is read from.  Everything else is batch_rays_u8_kernel operand for operand.
-__global__ void __launch_bounds__(256)
-batch_rays_u8_depth_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, uint32_t W,
-                           uint32_t HW, float fx, float fy, float cx, float cy, const uint32_t* __restrict__ bank /*[V,HW]*/,
-                           const float* __restrict__ depth_bank /*[V,HW]*/, const float* __restrict__ lut /*[2,256]*/,
-                           const float* __restrict__ aabb, float min_near, float* __restrict__ rays_o, float* __restrict__ rays_d,
-                           float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ noises,
-                           float* __restrict__ bg, float* __restrict__ gt_depth, int32_t* __restrict__ counter,
-                           const float* __restrict__ cam_near_far /*[V,2] or NULL*/) {
+template <bool U8, bool KP>
+__global__ void __launch_bounds__(256) batch_rays_kernel(const BatchRaysK k) {
     const uint32_t n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0 && counter) counter[0] = 0;
-    if (n >= N) return;
-    const float* __restrict__ un = u + (size_t)n * 6;
-    const uint32_t v = view_of_uniform(un[0], V), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
-    const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
-    const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
-    const float* __restrict__ P = poses + (size_t)v * 16;
-    float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
-        o[k] = P[4 * k + 3];
-        rays_d[(size_t)n * 3 + k] = d[k];
-        rays_o[(size_t)n * 3 + k] = o[k];
+    if (n >= k.N) return;
+    if constexpr (KP) {
+        const float depth = k.kp_depth[n], weight = k.kp_weight[n];
+        // (row, col) clamped to the image: the loader clips them already, the clamp keeps a hand-made table inside the bank
+        const uint32_t row = (uint32_t)min(max(k.coords[(size_t)n * 2], 0), (int32_t)k.H - 1);
+        const uint32_t col = (uint32_t)min(max(k.coords[(size_t)n * 2 + 1], 0), (int32_t)k.W - 1);
+        batch_ray<U8>(k, n, k.view, col, row, k.fx, k.fy, k.cx, k.cy);
+        k.gt_depth[n] = depth;
+        k.depth_weight[n] = weight;
+    } else {
+        const float* un = k.u + (size_t)n * 6;
+        const uint32_t v = view_of_uniform(un[0], k.V), p = min(k.HW - 1u, (uint32_t)(un[1] * (float)k.HW));
+        float fx = k.fx, fy = k.fy, cx = k.cx, cy = k.cy;
+        if (k.intrinsics) {
+            const float4 K = k.intrinsics[v];
+            fx = K.x; fy = K.y; cx = K.z; cy = K.w;
+        }
+        batch_ray<U8>(k, n, v, p % k.W, p / k.W, fx, fy, cx, cy);
     }
-    const size_t at = (size_t)v * HW + (size_t)p;
-    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = decode_rgba8(bank[at], lut);
-    gt_depth[n] = depth_bank[at];
-    float tn, tf;
-    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
-    if (cam_near_far) {
-        tn = fmaxf(tn, cam_near_far[2 * v]);
-        tf = fminf(tf, cam_near_far[2 * v + 1]);
-    }
-    nears[n] = tn; fars[n] = tf;
-    noises[n] = un[2];
-    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
-}
-
-// batch_rays_u8_kernel / batch_rays_u8_depth_kernel for a set with PER-VIEW intrinsics (nerf/colmap_provider.py:521,540, nerf/dtu_provider.py:265):
-// ray n takes row v of intrinsics [V,4] = (fx, fy, cx, cy) -- one 16-byte load at the view index it already has; the table is V x 16 bytes
-// and stays in cache.  depth_bank / gt_depth are both set or both NULL (the plain batch).  Everything else is batch_rays_u8_kernel operand
-// for operand, so a table of equal rows gives its bits.
-__global__ void __launch_bounds__(256)
-batch_rays_u8_pv_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, uint32_t W,
-                        uint32_t HW, const float4* __restrict__ intrinsics /*[V] (fx, fy, cx, cy)*/, const uint32_t* __restrict__ bank /*[V,HW]*/,
-                        const float* __restrict__ depth_bank /*[V,HW] or NULL*/, const float* __restrict__ lut /*[2,256]*/,
-                        const float* __restrict__ aabb, float min_near, float* __restrict__ rays_o, float* __restrict__ rays_d,
-                        float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ noises,
-                        float* __restrict__ bg, float* __restrict__ gt_depth /*[N] or NULL*/, int32_t* __restrict__ counter,
-                        const float* __restrict__ cam_near_far /*[V,2] or NULL*/) {
-    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0 && counter) counter[0] = 0;
-    if (n >= N) return;
-    const float* __restrict__ un = u + (size_t)n * 6;
-    const uint32_t v = view_of_uniform(un[0], V), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
-    const float4 K = intrinsics[v];
-    const float fx = K.x, fy = K.y, cx = K.z, cy = K.w;
-    const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
-    const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
-    const float* __restrict__ P = poses + (size_t)v * 16;
-    float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
-        o[k] = P[4 * k + 3];
-        rays_d[(size_t)n * 3 + k] = d[k];
-        rays_o[(size_t)n * 3 + k] = o[k];
-    }
-    const size_t at = (size_t)v * HW + (size_t)p;
-    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = decode_rgba8(bank[at], lut);
-    if (depth_bank) gt_depth[n] = depth_bank[at];
-    float tn, tf;
-    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
-    if (cam_near_far) {
-        tn = fmaxf(tn, cam_near_far[2 * v]);
-        tf = fminf(tf, cam_near_far[2 * v + 1]);
-    }
-    nears[n] = tn; fars[n] = tf;
-    noises[n] = un[2];
-    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
+    if (n == 0 && k.counter) k.counter[0] = 0;
 }
 
 // One view of the dense-depth bank (capture.dense_depth_fill): dst [H,W] = bilinear(src [h,w]) * scale + bias with cv2.INTER_LINEAR's
@@ -262,54 +190,38 @@ capture_box_downscale_kernel(const uint32_t* __restrict__ src /*[V,H,W]*/, uint3
 
 }   // namespace
 
-extern "C" int n2m_batch_rays_u8(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
-                                 float cx, float cy, const uint32_t* bank, const float* lut, const float* aabb, float min_near, float* rays_o,
-                                 float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg, int32_t* counter,
-                                 const float* cam_near_far, void* stream) {
-    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(bank); N2M_NOTNULL(lut); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o); N2M_NOTNULL(rays_d);
-    N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises);
-    N2M_REQUIRE(V >= 1 && H >= 1 && W >= 1 && (uint64_t)H * W < (1ull << 24), N2M_EINVAL,
-                "batch_rays_u8: need V >= 1 and 1 <= H*W < 2^24 (pixel index from an fp32 uniform)");
-    if (N == 0) return 0;
-    batch_rays_u8_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W, fx, fy, cx, cy, bank, lut, aabb,
-                                                                                min_near, rays_o, rays_d, rgba, nears, fars, noises, bg, counter,
-                                                                                cam_near_far);
-    N2M_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int n2m_batch_rays_u8_depth(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
-                                       float cx, float cy, const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb,
-                                       float min_near, float* rays_o, float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg,
-                                       float* gt_depth, int32_t* counter, const float* cam_near_far, void* stream) {
-    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(bank); N2M_NOTNULL(depth_bank); N2M_NOTNULL(lut); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o);
-    N2M_NOTNULL(rays_d); N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises); N2M_NOTNULL(gt_depth);
-    N2M_REQUIRE(V >= 1 && H >= 1 && W >= 1 && (uint64_t)H * W < (1ull << 24), N2M_EINVAL,
-                "batch_rays_u8_depth: need V >= 1 and 1 <= H*W < 2^24 (pixel index from an fp32 uniform)");
-    if (N == 0) return 0;
-    batch_rays_u8_depth_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W, fx, fy, cx, cy, bank, depth_bank,
-                                                                                      lut, aabb, min_near, rays_o, rays_d, rgba, nears, fars, noises,
-                                                                                      bg, gt_depth, counter, cam_near_far);
-    N2M_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int n2m_batch_rays_u8_pv(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, const float* intrinsics,
-                                    const uint32_t* bank, const float* depth_bank, const float* lut, const float* aabb, float min_near,
-                                    float* rays_o, float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth,
-                                    int32_t* counter, const float* cam_near_far, void* stream) {
-    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(intrinsics); N2M_NOTNULL(bank); N2M_NOTNULL(lut); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o);
-    N2M_NOTNULL(rays_d); N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises);
-    N2M_REQUIRE((depth_bank == nullptr) == (gt_depth == nullptr), N2M_ENULL,
-                "batch_rays_u8_pv: depth_bank and gt_depth are both set or both NULL, %s is NULL", depth_bank == nullptr ? "depth_bank" : "gt_depth");
-    N2M_REQUIRE(V >= 1 && H >= 1 && W >= 1 && (uint64_t)H * W < (1ull << 24), N2M_EINVAL,
-                "batch_rays_u8_pv: need V >= 1 and 1 <= H*W < 2^24 (pixel index from an fp32 uniform)");
-    N2M_REQUIRE(((uintptr_t)intrinsics & 15u) == 0, N2M_EINVAL, "batch_rays_u8_pv: intrinsics [V,4] must be 16-byte aligned (one load per ray)");
-    if (N == 0) return 0;
-    batch_rays_u8_pv_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W,
-                                                                                   reinterpret_cast<const float4*>(intrinsics), bank, depth_bank, lut,
-                                                                                   aabb, min_near, rays_o, rays_d, rgba, nears, fars, noises, bg,
-                                                                                   gt_depth, counter, cam_near_far);
+extern "C" int n2m_batch_rays(const N2mBatchRays* d, void* stream) {
+    N2M_NOTNULL(d);
+    N2M_NOTNULL(d->poses); N2M_NOTNULL(d->uniforms); N2M_NOTNULL(d->aabb); N2M_NOTNULL(d->rays_o); N2M_NOTNULL(d->rays_d); N2M_NOTNULL(d->rgba);
+    N2M_NOTNULL(d->nears); N2M_NOTNULL(d->fars); N2M_NOTNULL(d->noises);
+    const bool u8 = d->bank != nullptr, kp = d->coords != nullptr;
+    N2M_REQUIRE(u8 || d->images != nullptr, N2M_ENULL, "batch_rays: no ground truth, images (fp32) and bank (RGBA8 words) are both NULL");
+    N2M_REQUIRE(!u8 || d->images == nullptr, N2M_EINVAL, "batch_rays: images (fp32) and bank (RGBA8 words) are mutually exclusive");
+    N2M_REQUIRE(d->intrinsics != nullptr || (d->fx != 0.f && d->fy != 0.f), N2M_EINVAL, "batch_rays: intrinsics is NULL and the scalar fx / fy are zero");
+    if (u8) N2M_NOTNULL(d->lut);
+    N2M_REQUIRE(d->V >= 1 && d->H >= 1 && d->W >= 1 && (uint64_t)d->H * d->W < (1ull << 24), N2M_EINVAL,
+                "batch_rays: need V >= 1 and 1 <= H*W < 2^24 (pixel index from an fp32 uniform)");
+    if (kp) {       // the keypoints [first, first + N) of the sparse-depth table belong to `view`; coords / kp_depth / kp_weight are the WHOLE table's arrays
+        N2M_NOTNULL(d->bank); N2M_NOTNULL(d->kp_depth); N2M_NOTNULL(d->kp_weight); N2M_NOTNULL(d->gt_depth); N2M_NOTNULL(d->depth_weight);
+        N2M_REQUIRE(d->intrinsics == nullptr && d->depth_bank == nullptr, N2M_EINVAL,
+                    "batch_rays: a keypoint batch takes its view's four scalar intrinsics and its depth from the keypoints");
+        N2M_REQUIRE(d->view < d->V && (uint64_t)d->first + d->N < (1ull << 31), N2M_EINVAL, "batch_rays: need view < V and first + K < 2^31");
+    } else {
+        N2M_REQUIRE((d->depth_bank == nullptr) == (d->gt_depth == nullptr), N2M_ENULL,
+                    "batch_rays: depth_bank and gt_depth are both set or both NULL, %s is NULL", d->depth_bank == nullptr ? "depth_bank" : "gt_depth");
+        N2M_REQUIRE(d->depth_bank == nullptr || u8, N2M_EUNSUPPORTED, "batch_rays: the depth gather is built beside the RGBA8 bank only");
+        N2M_REQUIRE(((uintptr_t)d->intrinsics & 15u) == 0, N2M_EINVAL, "batch_rays: intrinsics [V,4] must be 16-byte aligned (one load per ray)");
+    }
+    if (d->N == 0) return 0;
+    const BatchRaysK k{d->poses, d->uniforms, d->V, d->N, d->H, d->W, d->H * d->W, d->fx, d->fy, d->cx, d->cy,
+                       reinterpret_cast<const float4*>(d->intrinsics), d->images, d->bank, d->lut, d->depth_bank,
+                       kp ? d->coords + (size_t)d->first * 2 : nullptr, kp ? d->kp_depth + d->first : nullptr, kp ? d->kp_weight + d->first : nullptr,
+                       d->view, d->aabb, d->min_near, d->cam_near_far, d->rays_o, d->rays_d, d->rgba, d->nears, d->fars, d->noises, d->bg,
+                       d->gt_depth, d->depth_weight, d->counter};
+    const dim3 grid(n2m_ceil_div(d->N, 256));
+    if (kp) batch_rays_kernel<true, true><<<grid, 256, 0, (hipStream_t)stream>>>(k);
+    else if (u8) batch_rays_kernel<true, false><<<grid, 256, 0, (hipStream_t)stream>>>(k);
+    else batch_rays_kernel<false, false><<<grid, 256, 0, (hipStream_t)stream>>>(k);
     N2M_CHECK_LAUNCH();
     return 0;
 }
@@ -329,26 +241,6 @@ extern "C" int n2m_depth_bank_fill(const float* src, uint32_t h, uint32_t w, uin
     N2M_REQUIRE(h >= 1 && w >= 1 && H >= 1 && W >= 1 && h < (1u << 24) && w < (1u << 24) && (uint64_t)H * W < (1ull << 32), N2M_EINVAL,
                 "depth_bank_fill: need 1 <= h, w < 2^24 and 1 <= H*W < 2^32");
     depth_bank_fill_kernel<<<n2m_ceil_div((uint64_t)H * W, 256), 256, 0, (hipStream_t)stream>>>(src, h, w, H, W, ry, rx, scale, bias, dst);
-    N2M_CHECK_LAUNCH();
-    return 0;
-}
-
-// The keypoints [first, first + K) of the sparse-depth table belong to `view`; coords / kp_depth / kp_weight are the WHOLE table's arrays.
-extern "C" int n2m_batch_rays_sparse_u8(const float* poses, const float* uniforms, uint32_t V, uint32_t view, uint32_t first, uint32_t K, uint32_t H,
-                                        uint32_t W, float fx, float fy, float cx, float cy, const uint32_t* bank, const float* lut, const float* aabb,
-                                        float min_near, const int32_t* coords, const float* kp_depth, const float* kp_weight, float* rays_o,
-                                        float* rays_d, float* rgba, float* nears, float* fars, float* noises, float* bg, float* gt_depth,
-                                        float* depth_weight, int32_t* counter, const float* cam_near_far, void* stream) {
-    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(bank); N2M_NOTNULL(lut); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o); N2M_NOTNULL(rays_d);
-    N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises); N2M_NOTNULL(coords); N2M_NOTNULL(kp_depth); N2M_NOTNULL(kp_weight);
-    N2M_NOTNULL(gt_depth); N2M_NOTNULL(depth_weight);
-    N2M_REQUIRE(view < V && H >= 1 && W >= 1 && (uint64_t)H * W < (1ull << 24) && (uint64_t)first + K < (1ull << 31), N2M_EINVAL,
-                "batch_rays_sparse_u8: need view < V, 1 <= H*W < 2^24 and first + K < 2^31");
-    if (K == 0) return 0;
-    batch_rays_sparse_u8_kernel<<<n2m_ceil_div(K, 256), 256, 0, (hipStream_t)stream>>>(
-        poses + (size_t)view * 16, uniforms, K, H, W, fx, fy, cx, cy, bank + (size_t)view * H * W, lut, aabb, min_near, coords + (size_t)first * 2,
-        kp_depth + first, kp_weight + first, rays_o, rays_d, rgba, nears, fars, noises, bg, gt_depth, depth_weight, counter,
-        cam_near_far ? cam_near_far + (size_t)view * 2 : nullptr);
     N2M_CHECK_LAUNCH();
     return 0;
 }

@@ -34,45 +34,6 @@ __global__ void near_far_kernel(const float* __restrict__ rays_o, const float* _
     n2m_near_far_of(o, d, aabb, min_near, nears[n], fars[n]);
 }
 
-// A whole training batch from ONE tensor of uniforms u [N,6] in [0,1): view = floor(u0 V), pixel = floor(u1 H W) (random_image_batch,
-// nerf/provider.py:302-303 + get_rays with N random pixels, nerf/utils.py:271), rays exactly as n2m_get_rays builds them
-// (nerf/utils.py:242-290), ground-truth gather (nerf/provider.py:330), near/far exactly as n2m_near_far_from_aabb, march jitter u2,
-// random background u3..u5 (nerf/utils.py:649-652); also clears the marcher's sample counter.  Seven small launches of the step's
-// side stream become one (they ran 7-13 us EACH beside the optimizer update and delayed the march behind them).
-__global__ void __launch_bounds__(256)
-batch_rays_kernel(const float* __restrict__ poses /*[V,4,4]*/, const float* __restrict__ u /*[N,6]*/, uint32_t V, uint32_t N, uint32_t W,
-                  uint32_t HW, float fx, float fy, float cx, float cy, const float* __restrict__ images /*[V,HW,4]*/,
-                  const float* __restrict__ aabb, float min_near, float* __restrict__ rays_o, float* __restrict__ rays_d,
-                  float* __restrict__ rgba, float* __restrict__ nears, float* __restrict__ fars, float* __restrict__ noises,
-                  float* __restrict__ bg, int32_t* __restrict__ counter, const float* __restrict__ cam_near_far /*[V,2] or NULL*/) {
-    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
-    if (n == 0 && counter) counter[0] = 0;
-    if (n >= N) return;
-    const float* __restrict__ un = u + (size_t)n * 6;
-    const uint32_t v = min(V - 1u, (uint32_t)(un[0] * (float)V)), p = min(HW - 1u, (uint32_t)(un[1] * (float)HW));
-    const float i = (float)(p % W) + 0.5f, j = (float)(p / W) + 0.5f;
-    const float d0 = (i - cx) / fx, d1 = -(j - cy) / fy, d2 = -1.0f;
-    const float* __restrict__ P = poses + (size_t)v * 16;
-    float o[3], d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        d[k] = (d0 * P[4 * k] + d1 * P[4 * k + 1]) + d2 * P[4 * k + 2];
-        o[k] = P[4 * k + 3];
-        rays_d[(size_t)n * 3 + k] = d[k];
-        rays_o[(size_t)n * 3 + k] = o[k];
-    }
-    *reinterpret_cast<float4*>(rgba + (size_t)n * 4) = *reinterpret_cast<const float4*>(images + ((size_t)v * HW + (size_t)p) * 4);
-    float tn, tf;
-    n2m_near_far_of(o, d, aabb, min_near, tn, tf);
-    if (cam_near_far) {       // per-view clamp from the sparse points (nerf/renderer.py:689-691, colmap_provider.py:563-565): maximum / minimum
-        tn = fmaxf(tn, cam_near_far[2 * v]);
-        tf = fminf(tf, cam_near_far[2 * v + 1]);
-    }
-    nears[n] = tn; fars[n] = tf;
-    noises[n] = un[2];
-    if (bg) { bg[(size_t)n * 3] = un[3]; bg[(size_t)n * 3 + 1] = un[4]; bg[(size_t)n * 3 + 2] = un[5]; }
-}
-
 __global__ void sph_from_ray_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, float radius,
                                     uint32_t N, float* __restrict__ coords) {
     const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1269,7 +1230,7 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
             block_live_out[blockIdx.x] = c;
         }
         last_block = false;
-        if (ticket) {           // ticket == NULL: the caller reduces the partials itself (n2m_scaler_update_slots_loss)
+        if (ticket) {           // ticket == NULL: the caller reduces the partials itself (n2m_scaler_update_slots)
             __threadfence();
             last_block = atomicAdd(ticket, 1u) == gridDim.x - 1;
         }
@@ -1382,27 +1343,6 @@ extern "C" int n2m_near_far_from_aabb(const float* rays_o, const float* rays_d, 
     near_far_kernel<<<n2m_ceil_div(N, 256), 256, 0, s>>>(rays_o, rays_d, aabb, N, min_near, nears, fars);
     N2M_CHECK_LAUNCH();
     return 0;
-}
-
-extern "C" int n2m_batch_rays_cnf(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
-                              float cx, float cy, const float* images, const float* aabb, float min_near, float* rays_o, float* rays_d,
-                              float* rgba, float* nears, float* fars, float* noises, float* bg, int32_t* counter, const float* cam_near_far,
-                                  void* stream) {
-    N2M_NOTNULL(poses); N2M_NOTNULL(uniforms); N2M_NOTNULL(images); N2M_NOTNULL(aabb); N2M_NOTNULL(rays_o); N2M_NOTNULL(rays_d);
-    N2M_NOTNULL(rgba); N2M_NOTNULL(nears); N2M_NOTNULL(fars); N2M_NOTNULL(noises);
-    N2M_REQUIRE(V >= 1 && (uint64_t)H * W < (1ull << 24), N2M_EINVAL, "batch_rays: need V >= 1 and H*W < 2^24 (pixel index from an fp32 uniform)");
-    if (N == 0) return 0;
-    batch_rays_kernel<<<n2m_ceil_div(N, 256), 256, 0, (hipStream_t)stream>>>(poses, uniforms, V, N, W, H * W, fx, fy, cx, cy, images, aabb, min_near,
-                                                                             rays_o, rays_d, rgba, nears, fars, noises, bg, counter, cam_near_far);
-    N2M_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int n2m_batch_rays(const float* poses, const float* uniforms, uint32_t V, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
-                              float cx, float cy, const float* images, const float* aabb, float min_near, float* rays_o, float* rays_d,
-                              float* rgba, float* nears, float* fars, float* noises, float* bg, int32_t* counter, void* stream) {
-    return n2m_batch_rays_cnf(poses, uniforms, V, N, H, W, fx, fy, cx, cy, images, aabb, min_near, rays_o, rays_d, rgba, nears, fars, noises, bg,
-                              counter, nullptr, stream);
 }
 
 extern "C" int n2m_sph_from_ray(const float* rays_o, const float* rays_d, float radius, uint32_t N, float* coords,
@@ -1705,20 +1645,6 @@ extern "C" int n2m_composite_rays_train_forward(const float* sigmas, const float
     return 0;
 }
 
-// Training fast path: compositing, loss head and both backward passes of n2m_composite_rays_train_forward/backward +
-// n2m_photo_loss_forward/backward in one launch (density mode; no grad_weights / grad_depth: the plain rgb + mask loss).
-// Optional outputs of the NEXT n2m_composite_loss_train* calls of this thread (sticky until cleared with NULLs): per ray the number of
-// samples up to and including the one the early stop fell on (every later sample of the ray receives exactly zero gradients: raymarching.cu:
-// 553,640 `break`), and their sums per workgroup of 16 rays.  n2m_sample_order_live_first turns them into the order the table backward wants.
-static thread_local int32_t* g_live_out = nullptr;
-static thread_local uint32_t* g_block_live_out = nullptr;
-extern "C" int n2m_composite_live_counts(int32_t* live /*[N]*/, uint32_t* block_live /*[ceil(N / 16)]*/) {
-    N2M_REQUIRE((live == nullptr) == (block_live == nullptr), N2M_ENULL, "n2m_composite_live_counts: both outputs or neither");
-    g_live_out = live;
-    g_block_live_out = block_live;
-    return 0;
-}
-
 // perm[0 .. M) <- the samples of a marched batch with every ray's live prefix first (ray order, sample order inside a ray), then every
 // ray's dead tail (same order): position of sample off_r + k = live_before(r) + k for k < live_r, else M_live + (off_r - live_before(r)) +
 // (k - live_r).  One launch: a workgroup owns 16 rays (one workgroup of the compositing kernel) and derives its two offsets from the
@@ -1778,74 +1704,33 @@ extern "C" int n2m_sample_order_live_first(const int32_t* rays, const int32_t* l
     return 0;
 }
 
-extern "C" int n2m_composite_loss_train_ex(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                                        float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb,
-                                        float lambda_mask, const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas,
-                                        float* grad_rgbs, float* partial, uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy,
-                                            int alpha_mode, void* stream) {
-    N2M_NOTNULL(rays); N2M_NOTNULL(gt_rgba); N2M_NOTNULL(grad_loss); N2M_NOTNULL(partial);
-    N2M_REQUIRE(ticket == nullptr || loss != nullptr, N2M_ENULL, "composite_loss_train: a ticket needs the loss output");
-    if (M > 0) { N2M_NOTNULL(sigmas); N2M_NOTNULL(rgbs); N2M_NOTNULL(ts); N2M_NOTNULL(grad_sigmas); N2M_NOTNULL(grad_rgbs); }
+// Training fast path: compositing, loss head and both backward passes of n2m_composite_rays_train_forward/backward +
+// n2m_photo_loss_forward/backward in one launch.  One dispatch over the kernel's instantiations: DEPTH when the call has a depth target or
+// asks for the depth output (density mode only), else ALPHA, else ENT by lambda_entropy.  live / block_live (optional): per ray the number of
+// samples up to and including the one the early stop fell on (every later sample of the ray receives exactly zero gradients: raymarching.cu:
+// 553,640 `break`), and their sums per workgroup of 16 rays.  n2m_sample_order_live_first turns them into the order the table backward wants.
+extern "C" int n2m_composite_loss_train(const N2mCompositeLoss* d, void* stream) {
+    N2M_NOTNULL(d);
+    const bool with_depth = d->gt_depth != nullptr || d->depth != nullptr;
+    N2M_REQUIRE(!(d->alpha_mode && with_depth), N2M_EUNSUPPORTED, "composite_loss_train: the depth term is built for density mode only");
+    N2M_NOTNULL(d->rays); N2M_NOTNULL(d->gt_rgba); N2M_NOTNULL(d->grad_loss); N2M_NOTNULL(d->partial);
+    N2M_REQUIRE(d->ticket == nullptr || d->loss != nullptr, N2M_ENULL, "composite_loss_train: a ticket needs the loss output");
+    N2M_REQUIRE((d->live == nullptr) == (d->block_live == nullptr), N2M_ENULL, "composite_loss_train: live and block_live, both outputs or neither");
+    N2M_REQUIRE(!(d->alpha_mode && d->lambda_entropy > 0.0f), N2M_EUNSUPPORTED, "composite_loss_train: alpha mode with the entropy term is not built");
+    const uint32_t M = d->M, N = d->N;
+    if (M > 0) { N2M_NOTNULL(d->sigmas); N2M_NOTNULL(d->rgbs); N2M_NOTNULL(d->ts); N2M_NOTNULL(d->grad_sigmas); N2M_NOTNULL(d->grad_rgbs); }
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    N2M_PROF_K(N2M_K_COMPOSITE_FWD, s, 28.0 * M + 28.0 * N + 44.0 * M + 48.0 * N);     // forward + backward of SURVEY 8d, one launch
-    if (alpha_mode) {
-        N2M_REQUIRE(lambda_entropy <= 0.0f, N2M_EUNSUPPORTED, "composite_loss_train: alpha mode with the entropy term is not built");
-        N2M_LAUNCH((composite_loss_train_kernel<false, true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar,
-                                                                                     lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas,
-                                                                                     grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, g_live_out, g_block_live_out, CompositeDepthArgs{});
-    } else if (lambda_entropy > 0.0f)
-        N2M_LAUNCH((composite_loss_train_kernel<true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar,
-                                                                              lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas,
-                                                                              grad_rgbs, partial, ticket, loss, loss_sum, lambda_entropy, g_live_out, g_block_live_out, CompositeDepthArgs{});
-    else
-        N2M_LAUNCH((composite_loss_train_kernel<false>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar,
-                                                                               lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas,
-                                                                               grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, g_live_out, g_block_live_out, CompositeDepthArgs{});
-    N2M_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int n2m_composite_loss_train_ent(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                                            float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb,
-                                            float lambda_mask, const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas,
-                                            float* grad_rgbs, float* partial, uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy,
-                                            void* stream) {
-    return n2m_composite_loss_train_ex(sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar, lambda_rgb, lambda_mask, grad_loss, weights_sum,
-                                       image, grad_sigmas, grad_rgbs, partial, ticket, loss, loss_sum, lambda_entropy, 0, stream);
-}
-
-extern "C" int n2m_composite_loss_train(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                                        float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb,
-                                        float lambda_mask, const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas,
-                                        float* grad_rgbs, float* partial, uint32_t* ticket, float* loss, float* loss_sum, void* stream) {
-    return n2m_composite_loss_train_ent(sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg, bg_scalar, lambda_rgb, lambda_mask, grad_loss,
-                                        weights_sum, image, grad_sigmas, grad_rgbs, partial, ticket, loss, loss_sum, 0.0f, stream);
-}
-
-// ... + the sparse-depth term (DEPTH instantiations of the same kernel; density mode only)
-extern "C" int n2m_composite_loss_train_depth(const float* sigmas, const float* rgbs, const float* ts, const int32_t* rays, uint32_t M, uint32_t N,
-                                              float T_thresh, const float* gt_rgba, const float* bg, float bg_scalar, float lambda_rgb,
-                                              float lambda_mask, const float* grad_loss, float* weights_sum, float* image, float* grad_sigmas,
-                                              float* grad_rgbs, float* partial, uint32_t* ticket, float* loss, float* loss_sum, float lambda_entropy,
-                                              float* depth, const float* gt_depth, const float* depth_weight, float lambda_depth, int alpha_mode,
-                                              void* stream) {
-    N2M_REQUIRE(!alpha_mode, N2M_EUNSUPPORTED, "composite_loss_train_depth: the depth term is built for density mode only");
-    N2M_NOTNULL(rays); N2M_NOTNULL(gt_rgba); N2M_NOTNULL(grad_loss); N2M_NOTNULL(partial);
-    N2M_REQUIRE(ticket == nullptr || loss != nullptr, N2M_ENULL, "composite_loss_train: a ticket needs the loss output");
-    if (M > 0) { N2M_NOTNULL(sigmas); N2M_NOTNULL(rgbs); N2M_NOTNULL(ts); N2M_NOTNULL(grad_sigmas); N2M_NOTNULL(grad_rgbs); }
-    if (N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    N2M_PROF_K(N2M_K_COMPOSITE_FWD, s, 28.0 * M + 28.0 * N + 44.0 * M + 48.0 * N + 12.0 * N);   // + gt_depth, depth_weight read, depth stored
-    const CompositeDepthArgs da{depth, gt_depth, depth_weight, lambda_depth};
-    if (lambda_entropy > 0.0f)
-        N2M_LAUNCH((composite_loss_train_kernel<true, false, true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg,
-                   bg_scalar, lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas, grad_rgbs, partial, ticket, loss, loss_sum,
-                   lambda_entropy, g_live_out, g_block_live_out, da);
-    else
-        N2M_LAUNCH((composite_loss_train_kernel<false, false, true>), n2m_ceil_div(N, 16), 1024, 0, s, sigmas, rgbs, ts, rays, M, N, T_thresh, gt_rgba, bg,
-                   bg_scalar, lambda_rgb, lambda_mask, grad_loss, weights_sum, image, grad_sigmas, grad_rgbs, partial, ticket, loss, loss_sum, 0.0f,
-                   g_live_out, g_block_live_out, da);
+    // forward + backward of SURVEY 8d, one launch (+ gt_depth, depth_weight read, depth stored)
+    N2M_PROF_K(N2M_K_COMPOSITE_FWD, s, 28.0 * M + 28.0 * N + 44.0 * M + 48.0 * N + (with_depth ? 12.0 * N : 0.0));
+    const bool ent = d->lambda_entropy > 0.0f;
+    const CompositeDepthArgs da{d->depth, d->gt_depth, d->depth_weight, d->lambda_depth};
+    auto* kernel = with_depth       ? (ent ? composite_loss_train_kernel<true, false, true> : composite_loss_train_kernel<false, false, true>)
+                   : d->alpha_mode ? composite_loss_train_kernel<false, true>
+                                   : (ent ? composite_loss_train_kernel<true> : composite_loss_train_kernel<false>);
+    N2M_LAUNCH(kernel, n2m_ceil_div(N, 16), 1024, 0, s, d->sigmas, d->rgbs, d->ts, d->rays, M, N, d->T_thresh, d->gt_rgba, d->bg, d->bg_scalar,
+               d->lambda_rgb, d->lambda_mask, d->grad_loss, d->weights_sum, d->image, d->grad_sigmas, d->grad_rgbs, d->partial, d->ticket, d->loss,
+               d->loss_sum, ent ? d->lambda_entropy : 0.0f, d->live, d->block_live, da);
     N2M_CHECK_LAUNCH();
     return 0;
 }

@@ -631,33 +631,6 @@ adam_body(const AdamTensors& t, float beta1, float beta2, float omb1, float omb2
     }
 }
 
-// GradScaler.update() (torch/amp/grad_scaler.py:_amp_update_scale_) + step count + found_inf reset, one thread
-__global__ void scaler_update_kernel(float* scale, float* growth_tracker, float* found_inf, float* step, float* bias, double beta1,
-                                     double beta2, float growth_factor, float backoff_factor, float growth_interval) {
-    if (*found_inf != 0.0f) {
-        if (scale) *scale *= backoff_factor;
-        if (growth_tracker) *growth_tracker = 0.0f;
-    } else {
-        if (step) *step += 1.0f;
-        if (growth_tracker) {
-            const float ok = *growth_tracker + 1.0f;
-            if (ok >= growth_interval) {
-                const float ns = *scale * growth_factor;
-                if (scale && ns <= 3.0e38f) *scale = ns;            // do not grow into inf
-                *growth_tracker = 0.0f;
-            } else {
-                *growth_tracker = ok;
-            }
-        }
-    }
-    *found_inf = 0.0f;
-    if (step && bias) {                       // bias corrections of the NEXT step, in double like torch's host-side arithmetic
-        const double t = (double)*step + 1.0;
-        bias[0] = (float)(1.0 - pow(beta1, t));
-        bias[1] = (float)sqrt(1.0 - pow(beta2, t));
-    }
-}
-
 }  // namespace
 
 extern "C" int n2m_get_rays(const float* poses, const int64_t* cam, const int64_t* pix, uint32_t N, uint32_t H, uint32_t W, float fx, float fy,
@@ -977,7 +950,7 @@ adam_kernel(AdamTensors t, float beta1, float beta2, float omb1, float omb2, flo
 }
 
 // n2m_adam_step_scaler: the optimizer pass whose LAST workgroup to finish also does the GradScaler / step-count / loss-value bookkeeping that
-// n2m_scaler_update_slots_loss3 does as a one-workgroup launch behind it (scaler_update_slots_body: the same code walking the partials in the same
+// n2m_scaler_update_slots does as a one-workgroup launch behind it (scaler_update_slots_body: the same code walking the partials in the same
 // order -- identical bits).  Every wave reads found_inf / bias before its update and leaves an arrival mark when it is done; the one wave that waits
 // for all marks knows that nobody will read that state again in this launch and rewrites it for the next step.  No fence: the bookkeeping reads
 // nothing the other workgroups of this launch wrote.  Saves the step one launch on its critical path (a single workgroup that
@@ -990,13 +963,109 @@ struct ScalerTailK {
     const float* extra2_partial; uint32_t n_extra2; float extra2_scale;
     uint32_t* ticket;
 };
+
+// GradScaler.update() (torch/amp/grad_scaler.py:_amp_update_scale_) + found_inf reset, with one step count PER TENSOR SLOT (torch.optim.Adam keeps `state[p]["step"]` per parameter: a parameter that gets its
+// first gradient late -- nerf2mesh's specular head after `diffuse_step` -- starts its bias corrections at t = 1).  Thread 0 does the
+// scaler bookkeeping and the global count (slot 0), thread s the count and the next-step corrections of slot s.
+// (one body for the stand-alone launch further down -- a workgroup of `blockDim.x` threads, partial sums through LDS -- and for ONE WAVE at the end of
+//  adam_kernel_with_scaler below, ONE_WAVE = true: no LDS and no barrier in that kernel -- a kernel that has either gets its workgroups placed as
+//  units, which costs the optimizer pass of 18 000 short-lived workgroups 40 us, measured -- the wave walks the partials in the order a
+//  256-thread workgroup does: virtual wave w, lane l takes partials 64 w + l, + 256, ...; the same wave sums, added in wave order: identical bits)
 template <bool ONE_WAVE>
-__device__ __forceinline__ void scaler_update_slots_body(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                                         uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                                         float growth_interval, const float* __restrict__ loss_partial, uint32_t n_partial, float inv_rays,
-                                                         float* __restrict__ loss, float* __restrict__ loss_sum, const float* __restrict__ extra_partial,
-                                                         uint32_t n_extra, float extra_scale, const float* __restrict__ extra2_partial, uint32_t n_extra2,
-                                                         float extra2_scale);
+__device__ __forceinline__ void scaler_update_slots_body(const ScalerTailK& k) {
+    const uint32_t s = ONE_WAVE ? (threadIdx.x & 63u) : threadIdx.x;
+    float tot_part = 0.0f, tot_extra = 0.0f, tot_extra2 = 0.0f;       // thread 0: the three sums
+    bool ok;
+    if constexpr (ONE_WAVE) {
+        // (the 32 values of a chunk of 2 048 partials are requested together and added in order afterwards: one memory round trip per chunk -- the
+        //  plain loop's one round trip per value made this tail 45 us long)
+        auto sum256 = [&](const float* __restrict__ part, uint32_t n) {
+            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            for (uint32_t base = 0; base < n; base += 2048u) {
+                float x[8][4];
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; ++k)
+#pragma unroll
+                    for (uint32_t w = 0; w < 4u; ++w) {
+                        const uint32_t i = base + 256u * k + 64u * w + s;
+                        x[k][w] = i < n ? part[i] : 0.0f;
+                    }
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; ++k)
+#pragma unroll
+                    for (uint32_t w = 0; w < 4u; ++w)
+                        if (base + 256u * k + 64u * w + s < n) acc[w] += x[k][w];
+            }
+            float tot = 0.0f;
+#pragma unroll
+            for (uint32_t w = 0; w < 4u; ++w) tot += n2m_wave_sum(acc[w]);
+            return tot;
+        };
+        if (k.extra2_partial) tot_extra2 = sum256(k.extra2_partial, k.n_extra2);
+        if (k.extra_partial) tot_extra = sum256(k.extra_partial, k.n_extra);
+        if (k.loss_partial) tot_part = sum256(k.loss_partial, k.n_partial);
+        ok = *k.found_inf == 0.0f;                          // (one wave: every lane has its verdict before lane 0's store below is issued)
+    } else {
+        __shared__ float wave_part[16], wave_extra[16], wave_extra2[16];
+        if (k.extra2_partial) {     // a third term (SDF recipe: the eikonal loss, lambda / M x sum of (|normal| - 1)^2)
+            float acc = 0.0f;
+            for (uint32_t i = s; i < k.n_extra2; i += blockDim.x) acc += k.extra2_partial[i];
+            acc = n2m_wave_sum(acc);
+            if ((s & 63u) == 0u) wave_extra2[s >> 6] = acc;
+        }
+        if (k.extra_partial) {      // a second term of the loss value with its own normalisation (specular regulariser: lambda / M x sum of squares)
+            float acc = 0.0f;
+            for (uint32_t i = s; i < k.n_extra; i += blockDim.x) acc += k.extra_partial[i];
+            acc = n2m_wave_sum(acc);
+            if ((s & 63u) == 0u) wave_extra[s >> 6] = acc;
+        }
+        if (k.loss_partial) {       // the step's loss VALUE (nobody on the GPU waits for it): per-workgroup partials of n2m_composite_loss_train,
+            float acc = 0.0f;     // summed in a fixed order: thread j takes partials j, j + blockDim, ...; lanes in scan order; waves 0, 1, ...
+            for (uint32_t i = s; i < k.n_partial; i += blockDim.x) acc += k.loss_partial[i];      // (one wave did this alone: 17 serial round trips, 8 us)
+            acc = n2m_wave_sum(acc);
+            if ((s & 63u) == 0u) wave_part[s >> 6] = acc;
+        }
+        ok = *k.found_inf == 0.0f;
+        __syncthreads();                                  // everyone has read the verdict before thread 0 clears it
+        if (s == 0) {
+            for (uint32_t w = 0; w < (blockDim.x + 63u) / 64u; ++w) {
+                if (k.loss_partial) tot_part += wave_part[w];
+                if (k.extra_partial) tot_extra += wave_extra[w];
+                if (k.extra2_partial) tot_extra2 += wave_extra2[w];
+            }
+        }
+    }
+    if (k.loss_partial && s == 0) {
+        float v = tot_part * k.inv_rays;
+        if (k.extra_partial) v += tot_extra * k.extra_scale;
+        if (k.extra2_partial) v += tot_extra2 * k.extra2_scale;
+        if (k.loss) *k.loss = v;
+        if (k.loss_sum) *k.loss_sum += v;
+    }
+    if (s == 0) {
+        if (!ok) {
+            if (k.scale) *k.scale *= k.backoff_factor;
+            if (k.growth_tracker) *k.growth_tracker = 0.0f;
+        } else if (k.growth_tracker) {
+            const float g = *k.growth_tracker + 1.0f;
+            if (g >= k.growth_interval) {
+                const float ns = *k.scale * k.growth_factor;
+                if (k.scale && ns <= 3.0e38f) *k.scale = ns;            // do not grow into inf
+                *k.growth_tracker = 0.0f;
+            } else {
+                *k.growth_tracker = g;
+            }
+        }
+        *k.found_inf = 0.0f;
+    }
+    if (s <= N2M_ADAM_MAX) {
+        if (ok && (s == 0 || ((k.participants >> (s - 1u)) & 1u))) k.steps[s] += 1.0f;
+        const double t = (double)k.steps[s] + 1.0;      // corrections of this slot's NEXT step, in double like torch's host arithmetic
+        k.bias[2u * s] = (float)(1.0 - pow(k.beta1, t));
+        k.bias[2u * s + 1u] = (float)sqrt(1.0 - pow(k.beta2, t));
+    }
+}
+
 
 constexpr uint32_t kTailSlots = 64;        // arrival counters, one 128-byte line each (N2M_TAIL_TICKET_WORDS = 32 x this; 1 024 of them: no faster)
 // (the kernel's argument block as the hardware lays it out: where `tail` sits in the kernarg segment)
@@ -1041,10 +1110,18 @@ adam_kernel_with_scaler(AdamTensors t, float beta1, float beta2, float omb1, flo
 #pragma unroll
         for (uint32_t k = 0; k < kTailSlots / 64u; ++k) __hip_atomic_store(mine + 32u * 64u * k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    scaler_update_slots_body<true>(tp->scale, tp->growth_tracker, tp->found_inf, tp->steps, tp->bias, tp->participants, tp->beta1, tp->beta2,
-                                   tp->growth_factor, tp->backoff_factor, tp->growth_interval, tp->loss_partial, tp->n_partial, tp->inv_rays,
-                                   tp->loss, tp->loss_sum, tp->extra_partial, tp->n_extra, tp->extra_scale, tp->extra2_partial, tp->n_extra2,
-                                   tp->extra2_scale);
+    const ScalerTailK k = *tp;
+    scaler_update_slots_body<true>(k);
+}
+
+// the host descriptor as the kernels take it; without the loss partials there is no loss value and no term is summed
+static ScalerTailK scaler_tail_k(float* scale, float* found_inf, float* bias, double beta1, double beta2, const N2mScalerTail* t) {
+    const bool lp = t->loss_partial != nullptr;
+    const float* e1 = lp ? t->extra_partial : nullptr;
+    const float* e2 = lp ? t->extra2_partial : nullptr;
+    return ScalerTailK{scale, t->growth_tracker, found_inf, t->steps, bias, t->participants, beta1, beta2, t->growth_factor, t->backoff_factor,
+                       t->growth_interval, t->loss_partial, lp ? t->n_partial : 0u, lp ? 1.0f / (float)t->n_rays : 0.0f, lp ? t->loss : nullptr,
+                       lp ? t->loss_sum : nullptr, e1, e1 ? t->n_extra : 0u, t->extra_scale, e2, e2 ? t->n_extra2 : 0u, t->extra2_scale, t->ticket};
 }
 
 static int adam_step_impl(const N2mAdamDesc* d, double beta1, double beta2, float eps, const float* scale, const float* found_inf,
@@ -1144,11 +1221,7 @@ static int adam_step_impl(const N2mAdamDesc* d, double beta1, double beta2, floa
             N2M_REQUIRE(!peer, N2M_EUNSUPPORTED, "adam_step_scaler: not with the peer-store form");
             N2M_REQUIRE(tail->ticket && found_inf && tail->steps && tail->loss_partial && tail->n_rays > 0, N2M_ENULL,
                         "adam_step_scaler: NULL ticket / found_inf / steps / loss partials (or no rays)");
-            const ScalerTailK tk{const_cast<float*>(scale), tail->growth_tracker, const_cast<float*>(found_inf), tail->steps, const_cast<float*>(bias),
-                                 tail->participants, beta1, beta2, tail->growth_factor, tail->backoff_factor, tail->growth_interval, tail->loss_partial,
-                                 tail->n_partial, 1.0f / (float)tail->n_rays, tail->loss, tail->loss_sum, tail->extra_partial,
-                                 tail->extra_partial ? tail->n_extra : 0u, tail->extra_scale, tail->extra2_partial,
-                                 tail->extra2_partial ? tail->n_extra2 : 0u, tail->extra2_scale, tail->ticket};
+            const ScalerTailK tk = scaler_tail_k(const_cast<float*>(scale), const_cast<float*>(found_inf), const_cast<float*>(bias), beta1, beta2, tail);
             N2M_LAUNCH(adam_kernel_with_scaler, blocks, 256, 0, (hipStream_t)stream, t, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps,
                        scale, found_inf, bias, tk);
         } else if (peer)
@@ -1169,7 +1242,7 @@ extern "C" int n2m_adam_step(const N2mAdamDesc* d, double beta1, double beta2, f
 
 extern "C" int n2m_adam_step_scaler(const N2mAdamDesc* d, double beta1, double beta2, float eps, float* scale, float* found_inf, float* bias,
                                     const N2mScalerTail* tail, void* stream) {
-    N2M_REQUIRE(tail != nullptr, N2M_ENULL, "adam_step_scaler: NULL tail (use n2m_adam_step + n2m_scaler_update_slots_loss3)");
+    N2M_REQUIRE(tail != nullptr, N2M_ENULL, "adam_step_scaler: NULL tail (use n2m_adam_step + n2m_scaler_update_slots)");
     return adam_step_impl(d, beta1, beta2, eps, scale, found_inf, bias, nullptr, stream, tail);
 }
 
@@ -1179,178 +1252,23 @@ extern "C" int n2m_adam_step_peer(const N2mAdamDesc* d, double beta1, double bet
     return adam_step_impl(d, beta1, beta2, eps, scale, found_inf, bias, peer, stream);
 }
 
-// The same with one step count PER TENSOR SLOT (torch.optim.Adam keeps `state[p]["step"]` per parameter: a parameter that gets its
-// first gradient late -- nerf2mesh's specular head after `diffuse_step` -- starts its bias corrections at t = 1).  Thread 0 does the
-// scaler bookkeeping and the global count (slot 0), thread s the count and the next-step corrections of slot s.
-// (one body for the stand-alone launch below -- a workgroup of `blockDim.x` threads, partial sums through LDS -- and for ONE WAVE at the end of
-//  adam_kernel_with_scaler above, ONE_WAVE = true: no LDS and no barrier in that kernel -- a kernel that has either gets its workgroups placed as
-//  units, which costs the optimizer pass of 18 000 short-lived workgroups 40 us, measured -- the wave walks the partials in the order a
-//  256-thread workgroup does: virtual wave w, lane l takes partials 64 w + l, + 256, ...; the same wave sums, added in wave order: identical bits)
-template <bool ONE_WAVE>
-__device__ __forceinline__ void scaler_update_slots_body(float* scale, float* growth_tracker, float* found_inf, float* steps /*[1+MAX]*/,
-                                                         float* bias /*[1+MAX][2]*/, uint32_t participants, double beta1, double beta2,
-                                                         float growth_factor, float backoff_factor, float growth_interval,
-                                                         const float* __restrict__ loss_partial, uint32_t n_partial, float inv_rays,
-                                                         float* __restrict__ loss, float* __restrict__ loss_sum,
-                                                         const float* __restrict__ extra_partial, uint32_t n_extra, float extra_scale,
-                                                         const float* __restrict__ extra2_partial, uint32_t n_extra2, float extra2_scale) {
-    const uint32_t s = ONE_WAVE ? (threadIdx.x & 63u) : threadIdx.x;
-    float tot_part = 0.0f, tot_extra = 0.0f, tot_extra2 = 0.0f;       // thread 0: the three sums
-    bool ok;
-    if constexpr (ONE_WAVE) {
-        // (the 32 values of a chunk of 2 048 partials are requested together and added in order afterwards: one memory round trip per chunk -- the
-        //  plain loop's one round trip per value made this tail 45 us long)
-        auto sum256 = [&](const float* __restrict__ part, uint32_t n) {
-            float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (uint32_t base = 0; base < n; base += 2048u) {
-                float x[8][4];
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; ++k)
-#pragma unroll
-                    for (uint32_t w = 0; w < 4u; ++w) {
-                        const uint32_t i = base + 256u * k + 64u * w + s;
-                        x[k][w] = i < n ? part[i] : 0.0f;
-                    }
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; ++k)
-#pragma unroll
-                    for (uint32_t w = 0; w < 4u; ++w)
-                        if (base + 256u * k + 64u * w + s < n) acc[w] += x[k][w];
-            }
-            float tot = 0.0f;
-#pragma unroll
-            for (uint32_t w = 0; w < 4u; ++w) tot += n2m_wave_sum(acc[w]);
-            return tot;
-        };
-        if (extra2_partial) tot_extra2 = sum256(extra2_partial, n_extra2);
-        if (extra_partial) tot_extra = sum256(extra_partial, n_extra);
-        if (loss_partial) tot_part = sum256(loss_partial, n_partial);
-        ok = *found_inf == 0.0f;                          // (one wave: every lane has its verdict before lane 0's store below is issued)
-    } else {
-        __shared__ float wave_part[16], wave_extra[16], wave_extra2[16];
-        if (extra2_partial) {     // a third term (SDF recipe: the eikonal loss, lambda / M x sum of (|normal| - 1)^2)
-            float acc = 0.0f;
-            for (uint32_t i = s; i < n_extra2; i += blockDim.x) acc += extra2_partial[i];
-            acc = n2m_wave_sum(acc);
-            if ((s & 63u) == 0u) wave_extra2[s >> 6] = acc;
-        }
-        if (extra_partial) {      // a second term of the loss value with its own normalisation (specular regulariser: lambda / M x sum of squares)
-            float acc = 0.0f;
-            for (uint32_t i = s; i < n_extra; i += blockDim.x) acc += extra_partial[i];
-            acc = n2m_wave_sum(acc);
-            if ((s & 63u) == 0u) wave_extra[s >> 6] = acc;
-        }
-        if (loss_partial) {       // the step's loss VALUE (nobody on the GPU waits for it): per-workgroup partials of n2m_composite_loss_train,
-            float acc = 0.0f;     // summed in a fixed order: thread j takes partials j, j + blockDim, ...; lanes in scan order; waves 0, 1, ...
-            for (uint32_t i = s; i < n_partial; i += blockDim.x) acc += loss_partial[i];      // (one wave did this alone: 17 serial round trips, 8 us)
-            acc = n2m_wave_sum(acc);
-            if ((s & 63u) == 0u) wave_part[s >> 6] = acc;
-        }
-        ok = *found_inf == 0.0f;
-        __syncthreads();                                  // everyone has read the verdict before thread 0 clears it
-        if (s == 0) {
-            for (uint32_t w = 0; w < (blockDim.x + 63u) / 64u; ++w) {
-                if (loss_partial) tot_part += wave_part[w];
-                if (extra_partial) tot_extra += wave_extra[w];
-                if (extra2_partial) tot_extra2 += wave_extra2[w];
-            }
-        }
-    }
-    if (loss_partial && s == 0) {
-        float v = tot_part * inv_rays;
-        if (extra_partial) v += tot_extra * extra_scale;
-        if (extra2_partial) v += tot_extra2 * extra2_scale;
-        if (loss) *loss = v;
-        if (loss_sum) *loss_sum += v;
-    }
-    if (s == 0) {
-        if (!ok) {
-            if (scale) *scale *= backoff_factor;
-            if (growth_tracker) *growth_tracker = 0.0f;
-        } else if (growth_tracker) {
-            const float g = *growth_tracker + 1.0f;
-            if (g >= growth_interval) {
-                const float ns = *scale * growth_factor;
-                if (scale && ns <= 3.0e38f) *scale = ns;            // do not grow into inf
-                *growth_tracker = 0.0f;
-            } else {
-                *growth_tracker = g;
-            }
-        }
-        *found_inf = 0.0f;
-    }
-    if (s <= N2M_ADAM_MAX) {
-        if (ok && (s == 0 || ((participants >> (s - 1u)) & 1u))) steps[s] += 1.0f;
-        const double t = (double)steps[s] + 1.0;      // corrections of this slot's NEXT step, in double like torch's host arithmetic
-        bias[2u * s] = (float)(1.0 - pow(beta1, t));
-        bias[2u * s + 1u] = (float)sqrt(1.0 - pow(beta2, t));
-    }
-}
-
-__global__ void scaler_update_slots_kernel(float* scale, float* growth_tracker, float* found_inf, float* steps /*[1+MAX]*/,
-                                           float* bias /*[1+MAX][2]*/, uint32_t participants, double beta1, double beta2,
-                                           float growth_factor, float backoff_factor, float growth_interval,
-                                           const float* __restrict__ loss_partial, uint32_t n_partial, float inv_rays,
-                                           float* __restrict__ loss, float* __restrict__ loss_sum,
-                                           const float* __restrict__ extra_partial, uint32_t n_extra, float extra_scale,
-                                           const float* __restrict__ extra2_partial = nullptr, uint32_t n_extra2 = 0, float extra2_scale = 0.0f) {
+__global__ void scaler_update_slots_kernel(const ScalerTailK k) {
     __builtin_amdgcn_s_setprio(3);
-    scaler_update_slots_body<false>(scale, growth_tracker, found_inf, steps, bias, participants, beta1, beta2, growth_factor, backoff_factor, growth_interval,
-                             loss_partial, n_partial, inv_rays, loss, loss_sum, extra_partial, n_extra, extra_scale, extra2_partial, n_extra2, extra2_scale);
+    scaler_update_slots_body<false>(k);
 }
 
-extern "C" int n2m_scaler_update_slots(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                       uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                       float growth_interval, void* stream) {
-    N2M_REQUIRE(found_inf != nullptr && steps != nullptr && bias != nullptr, N2M_ENULL, "scaler_update_slots: NULL found_inf / steps / bias");
-    scaler_update_slots_kernel<<<1, 64, 0, (hipStream_t)stream>>>(scale, growth_tracker, found_inf, steps, bias, participants, beta1, beta2,
-                                                                  growth_factor, backoff_factor, growth_interval, nullptr, 0u, 0.0f, nullptr, nullptr, nullptr, 0u, 0.0f);
-    N2M_CHECK_LAUNCH();
-    return 0;
-}
-
-// The same + the final reduction of the loss value from the per-workgroup partials n2m_composite_loss_train leaves when it is given no
-// ticket (loss = sum(partial[0..n_partial)) / n_rays; *loss_sum += loss): keeps the arrival ticket -- one __threadfence + one same-address
-// atomic per workgroup -- out of the compositing kernel, whose loss VALUE nothing on the device waits for.
-extern "C" int n2m_scaler_update_slots_loss3(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                            uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                            float growth_interval, const float* loss_partial, uint32_t n_partial, uint32_t n_rays, float* loss,
-                                            float* loss_sum, const float* extra_partial, uint32_t n_extra, float extra_scale, const float* extra2_partial,
-                                             uint32_t n_extra2, float extra2_scale, void* stream) {
-    N2M_REQUIRE(found_inf != nullptr && steps != nullptr && bias != nullptr, N2M_ENULL, "scaler_update_slots: NULL found_inf / steps / bias");
-    N2M_REQUIRE(loss_partial != nullptr && n_rays > 0, N2M_EINVAL, "scaler_update_slots_loss: needs the loss partials and the ray count");
-    // 256 threads, not 1024: the launch sits on the main stream between Adam and the next forward while the side stream's marcher fills
-    // every CU, and a 16-wave workgroup then waits (measured: up to 27 us) for one CU to free 16 wave slots at once
-    scaler_update_slots_kernel<<<1, 256, 0, (hipStream_t)stream>>>(scale, growth_tracker, found_inf, steps, bias, participants, beta1, beta2,
-                                                                  growth_factor, backoff_factor, growth_interval, loss_partial, n_partial,
-                                                                  1.0f / (float)n_rays, loss, loss_sum, extra_partial, extra_partial ? n_extra : 0u, extra_scale,
-                                                                  extra2_partial, extra2_partial ? n_extra2 : 0u, extra2_scale);
-    N2M_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int n2m_scaler_update_slots_loss2(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                             uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                             float growth_interval, const float* loss_partial, uint32_t n_partial, uint32_t n_rays, float* loss,
-                                             float* loss_sum, const float* extra_partial, uint32_t n_extra, float extra_scale, void* stream) {
-    return n2m_scaler_update_slots_loss3(scale, growth_tracker, found_inf, steps, bias, participants, beta1, beta2, growth_factor, backoff_factor,
-                                         growth_interval, loss_partial, n_partial, n_rays, loss, loss_sum, extra_partial, n_extra, extra_scale,
-                                         nullptr, 0u, 0.0f, stream);
-}
-
-extern "C" int n2m_scaler_update_slots_loss(float* scale, float* growth_tracker, float* found_inf, float* steps, float* bias,
-                                            uint32_t participants, double beta1, double beta2, float growth_factor, float backoff_factor,
-                                            float growth_interval, const float* loss_partial, uint32_t n_partial, uint32_t n_rays, float* loss,
-                                            float* loss_sum, void* stream) {
-    return n2m_scaler_update_slots_loss2(scale, growth_tracker, found_inf, steps, bias, participants, beta1, beta2, growth_factor, backoff_factor,
-                                         growth_interval, loss_partial, n_partial, n_rays, loss, loss_sum, nullptr, 0u, 0.0f, stream);
-}
-
-extern "C" int n2m_scaler_update(float* scale, float* growth_tracker, float* found_inf, float* step, float* bias, double beta1,
-                                 double beta2, float growth_factor, float backoff_factor, float growth_interval, void* stream) {
-    N2M_REQUIRE(found_inf != nullptr, N2M_ENULL, "scaler_update: found_inf is NULL");
-    scaler_update_kernel<<<1, 1, 0, (hipStream_t)stream>>>(scale, growth_tracker, found_inf, step, bias, beta1, beta2, growth_factor,
-                                                           backoff_factor, growth_interval);
+// The stand-alone launch.  With the loss partials it also does the final reduction of the loss value n2m_composite_loss_train leaves to it
+// when it is given no ticket: keeps the arrival ticket -- one __threadfence + one same-address atomic per workgroup -- out of the compositing
+// kernel, whose loss VALUE nothing on the device waits for.
+extern "C" int n2m_scaler_update_slots(float* scale, float* found_inf, float* bias, double beta1, double beta2, const N2mScalerTail* tail,
+                                       void* stream) {
+    N2M_REQUIRE(tail != nullptr, N2M_ENULL, "scaler_update_slots: NULL tail");
+    N2M_REQUIRE(found_inf != nullptr && tail->steps != nullptr && bias != nullptr, N2M_ENULL, "scaler_update_slots: NULL found_inf / steps / bias");
+    N2M_REQUIRE(tail->loss_partial == nullptr || tail->n_rays > 0, N2M_EINVAL, "scaler_update_slots: the loss partials need the ray count");
+    // 64 threads for the bookkeeping alone; 256, not 1024, with the partials: the launch sits on the main stream between Adam and the next
+    // forward while the side stream's marcher fills every CU, and a 16-wave workgroup then waits (measured: up to 27 us) for one CU to free
+    // 16 wave slots at once
+    scaler_update_slots_kernel<<<1, tail->loss_partial ? 256 : 64, 0, (hipStream_t)stream>>>(scaler_tail_k(scale, found_inf, bias, beta1, beta2, tail));
     N2M_CHECK_LAUNCH();
     return 0;
 }

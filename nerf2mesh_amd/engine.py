@@ -11,7 +11,7 @@ streams, the random generators and torch.distributed -- and does the rest itself
   step (main stream, batch i):  n2m_grid_encode_forward_packed[_tvterms: one GPU, the lookup also leaves the backward's TV terms] ->
         n2m_field_forward -> n2m_composite_loss_train (compositing, loss head,
         both backward passes) -> n2m_field_backward -> n2m_grid_encode_backward_binned_pair (+TV) / ..._pair_tvt -> [world > 1: SUM all-reduce of the
-        fixed gradient buffers, fine levels first] -> n2m_adam_step -> n2m_scaler_update_slots_loss
+        fixed gradient buffers, fine levels first] -> n2m_adam_step -> n2m_scaler_update_slots
 
 Same kernels, same arguments, same random draws in the same order as Stage0Trainer: the two produce the same parameters
 (tests/test_engine.py).  What the reference does per iteration is cited there (nerf/utils.py:628-823,1152-1190, main.py:221-241).
@@ -89,7 +89,7 @@ class Stage0Engine:
         self.model, self.opt, self.device = model.to(device), opt, torch.device(device)
         dev = self.device
         # capture (capture.Capture, opt-in): a captured image set instead of the analytic box scene -- its poses, its intrinsics, its uint8
-        # bank (n2m_batch_rays_u8 in the place of n2m_batch_rays_cnf), its per-view depth ranges.  None: everything as it was.
+        # bank (n2m_batch_rays reads the bank in the place of the fp32 images), its per-view depth ranges.  None: everything as it was.
         self.capture = capture
         if capture is not None:
             capture.check_device(dev)
@@ -131,7 +131,7 @@ class Stage0Engine:
         # --enable_sparse_depth: one batch in ten is all keypoints of one view (capture.DepthSchedule, the same sequence as Stage0Trainer's); the
         # ray buffers are sized for the largest view from the start
         from .capture import dense_depth_for, depth_schedule_for
-        # --enable_dense_depth: EVERY batch gathers a depth target beside its colour (n2m_batch_rays_u8_depth) and every step runs the depth
+        # --enable_dense_depth: EVERY batch gathers a depth target beside its colour (n2m_batch_rays with the depth bank) and every step runs the depth
         # head with weight 1; N stays num_rays, so these steps steer adaptive_num_rays like plain ones.  One rank is what is tested.
         self.dense_depth = dense_depth_for(capture, opt)
         self.depth_schedule = depth_schedule_for(capture, opt, seed + rank)
@@ -182,7 +182,7 @@ class Stage0Engine:
         self.tv_fwd = (os.environ.get("N2M_TV_FWD", "1") != "0" and world_size == 1 and not opt.sdf and opt.lambda_tv > 0
                        and not self.tv_split and not self.tv_corners)
         # [round 6, MEASURED AND NOT ADOPTED: off by default, N2M_ADAM_TAIL=1 turns it on]  The scaler / step-count / loss-value bookkeeping behind the
-        # optimizer pass as the TAIL of that pass (n2m_adam_step_scaler: one wave of its last workgroup runs the code of n2m_scaler_update_slots_loss3
+        # optimizer pass as the TAIL of that pass (n2m_adam_step_scaler: one wave of its last workgroup runs the code of n2m_scaler_update_slots
         # once every other wave has left an arrival mark) instead of a one-workgroup launch of its own on the step's critical path (~10 us + the queue gap
         # in front of the next lookup).  Identical bits (tests/test_optim.py, tests/test_adam_tail.py) -- but the optimizer pass takes 136 us instead of 93
         # in the kernel that also holds the bookkeeping code, whatever the arrival scheme: step 0.540 -> 0.563 ms.
@@ -413,7 +413,7 @@ class Stage0Engine:
         self.model.update_extra_state()
 
     def _prepare(self, N, depth_view=None):
-        """Batch of N rays (depth_view: a depth batch, its N rays go through the keypoints of that view -- n2m_batch_rays_sparse_u8): pixel choice, rays + ground truth, near/far, march pass 1 (count + offset scan), count on its way to the host.
+        """Batch of N rays (depth_view: a depth batch, its N rays go through the keypoints of that view -- n2m_batch_rays in keypoint mode): pixel choice, rays + ground truth, near/far, march pass 1 (count + offset scan), count on its way to the host.
         Reads the cameras, the images and the occupancy bit field only."""
         opt, model, dev = self.opt, self.model, self.device
         cap = self.capture
@@ -820,6 +820,22 @@ class Stage0Engine:
                     continue
                 dist.all_gather_into_tensor(flat[lo * C:(lo + self.world * n) * C], flat[row0 * C:(row0 + n) * C].clone())
 
+    def _scaler_tail(self, participants, loss_out):
+        """N2mScalerTail of this step: the scaler / step-count bookkeeping and, with loss_out = (n_rays, loss buffer, (specular partials, scale)
+        or None[, (eikonal partials, count, scale)]), the step's loss value from the compositing kernel's per-workgroup partials."""
+        o = self.optimizer
+        gf, bf, gi = o.growth
+        tail = L.ScalerTail(growth_tracker=_p(o.growth_tracker), steps=_p(o.steps), participants=participants, growth_factor=gf, backoff_factor=bf,
+                            growth_interval=gi, ticket=_p(self._tail_ticket))
+        if loss_out is not None:
+            n_rays, buf, extra = loss_out[:3]
+            ex_buf, ex_scale = extra if extra is not None else (None, 0.0)
+            e2_buf, e2_n, e2_scale = loss_out[3] if len(loss_out) > 3 and loss_out[3] is not None else (None, 0, 0.0)
+            tail.loss_partial, tail.n_partial, tail.n_rays, tail.loss, tail.loss_sum = _p(self._w["partial"]), (n_rays + 15) // 16, n_rays, _p(buf), _p(self._loss_sum)
+            tail.extra_partial, tail.n_extra, tail.extra_scale = _p(ex_buf), self._n_spec, float(ex_scale)
+            tail.extra2_partial, tail.n_extra2, tail.extra2_scale = _p(e2_buf), int(e2_n), float(e2_scale)
+        return tail
+
     def _optimizer_step(self, full, lr_factor, loss_out=None, fused=None):
         o = self.optimizer
         self._wait_gather()          # (a step without samples ran no lookup: the rows the last gather sends must not be rewritten under it)
@@ -846,14 +862,7 @@ class Stage0Engine:
                    _p(o.bias), ctypes.addressof(self._adam_peer), s)
         elif (self.adam_tail and loss_out is not None and fused is None and self.peer is None and not self.shard):
             # optimizer pass + the scaler / step counts / loss value in one launch (the tail of the pass's last workgroup)
-            gf, bf, gi = o.growth
-            n_rays, buf, extra = loss_out[:3]
-            extra2 = loss_out[3] if len(loss_out) > 3 else None
-            ex_buf, ex_scale = extra if extra is not None else (None, 0.0)
-            e2_buf, e2_n, e2_scale = extra2 if extra2 is not None else (None, 0, 0.0)
-            tail = L.ScalerTail(_p(o.growth_tracker), _p(o.steps), participants, gf, bf, gi, _p(self._w["partial"]), (n_rays + 15) // 16, n_rays,
-                                _p(buf), _p(self._loss_sum), _p(ex_buf), self._n_spec, float(ex_scale), _p(e2_buf), int(e2_n), float(e2_scale),
-                                _p(self._tail_ticket))
+            tail = self._scaler_tail(participants, loss_out)
             L.call("n2m_adam_step_scaler", ctypes.addressof(desc), float(b1), float(b2), float(o.param_groups[0]["eps"]), _p(o.scale), _p(o.found_inf),
                    _p(o.bias), ctypes.addressof(tail), s)
             scaler_done = True
@@ -877,20 +886,9 @@ class Stage0Engine:
                 self._wait_gather()
         elif self.shard:
             self._gather_packed()
-        gf, bf, gi = o.growth
-        if scaler_done:
-            pass
-        elif loss_out is None:
-            L.call("n2m_scaler_update_slots", _p(o.scale), _p(o.growth_tracker), _p(o.found_inf), _p(o.steps), _p(o.bias), participants,
-                   float(b1), float(b2), gf, bf, gi, s)
-        else:        # + the step's loss value from the compositing kernel's per-workgroup partials
-            n_rays, buf, extra = loss_out[:3]
-            extra2 = loss_out[3] if len(loss_out) > 3 else None
-            ex_buf, ex_scale = extra if extra is not None else (None, 0.0)
-            e2_buf, e2_n, e2_scale = extra2 if extra2 is not None else (None, 0, 0.0)
-            L.call("n2m_scaler_update_slots_loss3", _p(o.scale), _p(o.growth_tracker), _p(o.found_inf), _p(o.steps), _p(o.bias), participants,
-                   float(b1), float(b2), gf, bf, gi, _p(self._w["partial"]), (n_rays + 15) // 16, n_rays, _p(buf), _p(self._loss_sum),
-                   _p(ex_buf), self._n_spec, float(ex_scale), _p(e2_buf), int(e2_n), float(e2_scale), s)
+        if not scaler_done:        # + the step's loss value from the compositing kernel's per-workgroup partials, when there is one
+            tail = self._scaler_tail(participants, loss_out)
+            L.call("n2m_scaler_update_slots", _p(o.scale), _p(o.found_inf), _p(o.bias), float(b1), float(b2), ctypes.addressof(tail), s)
         nxt = lr_lambda(self.global_step, self.opt.iters)          # like LambdaLR.step(): param_groups carry the NEXT step's rate
         for group in o.param_groups:
             group["lr"] = float(group["initial_lr"]) * nxt
@@ -1018,22 +1016,17 @@ class Stage0Engine:
         d_sigma, d_rgb = w["d_sr"][:max(M, 1)], w["d_sr"][max(M, 1):4 * max(M, 1)]
         # (+ the entropy regulariser of config 4, nerf/utils.py:728-733: its per-sample gradient is the backward's grad_weights)
         order = self.live_first and M > 0 and M <= (1 << 20) and self.peer is None
-        if order:
-            L.call("n2m_composite_live_counts", _p(w["live"]), _p(w["block_live"]))
-        try:
-            if b.depth_view is not None or self.dense_depth is not None:
-                # depth step (nerf/utils.py:685-705): the same head + the depth term -- the keypoints' depth and weight on a sparse-depth step,
-                # the bank's depth with weight 1 (depth_weight NULL) on every step of a dense-depth run
-                L.call("n2m_composite_loss_train_depth", _p(w["sigma"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb,
-                       lam_mask, _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, float(max(opt.lambda_entropy, 0.0)),
-                       None, _p(b.gtd), _p(b.dw) if b.depth_view is not None else None,
-                       float(opt.lambda_depth * min(1.0, self.global_step / 1000)), 0, s)
-            else:
-                L.call("n2m_composite_loss_train_ent", _p(w["sigma"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb, lam_mask,
-                       _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, float(max(opt.lambda_entropy, 0.0)), s)      # loss value: summed by the scaler kernel
-        finally:
-            if order:
-                L.call("n2m_composite_live_counts", None, None)
+        # depth step (nerf/utils.py:685-705): the same head + the depth term -- the keypoints' depth and weight on a sparse-depth step, the
+        # bank's depth with weight 1 (depth_weight NULL) on every step of a dense-depth run.  The loss value: summed by the scaler kernel.
+        depth_step = b.depth_view is not None or self.dense_depth is not None
+        head = L.CompositeLoss(sigmas=_p(w["sigma"]), rgbs=_p(w["rgb"]), ts=_p(ts), rays=_p(b.rays), M=M, N=N, T_thresh=1e-4, gt_rgba=_p(b.rgba),
+                               bg=_p(bg_t), bg_scalar=bg_s, lambda_rgb=lam_rgb, lambda_mask=lam_mask, grad_loss=_p(seed), grad_sigmas=_p(d_sigma),
+                               grad_rgbs=_p(d_rgb), partial=_p(w["partial"]), lambda_entropy=float(max(opt.lambda_entropy, 0.0)),
+                               live=_p(w["live"]) if order else None, block_live=_p(w["block_live"]) if order else None)
+        if depth_step:
+            head.gt_depth, head.depth_weight = _p(b.gtd), _p(b.dw) if b.depth_view is not None else None
+            head.lambda_depth = float(opt.lambda_depth * min(1.0, self.global_step / 1000))
+        L.call("n2m_composite_loss_train", ctypes.addressof(head), s)
         if order:
             L.call("n2m_sample_order_live_first", _p(b.rays), _p(w["live"]), _p(w["block_live"]), N, M, _p(w["perm"]), s)
             if self._identity_order:
@@ -1284,8 +1277,10 @@ class Stage0Engine:
             L.call("n2m_sdf_alpha_forward", _p(w["sigma"]), _p(sb["s6"]), _p(dirs), _p(ts), M, _p(model.variance), eps, car, _p(sb["alpha"]), None,
                    _p(sb["eik"]) if opt.lambda_eikonal > 0 else None, s)
         # compositing in alpha mode + loss head + their backward
-        L.call("n2m_composite_loss_train_ex", _p(sb["alpha"]), _p(w["rgb"]), _p(ts), _p(b.rays), M, N, 1e-4, _p(b.rgba), _p(bg_t), bg_s, lam_rgb, lam_mask,
-               _p(seed), None, None, _p(d_sigma), _p(d_rgb), _p(w["partial"]), None, None, None, 0.0, 1, s)
+        head = L.CompositeLoss(sigmas=_p(sb["alpha"]), rgbs=_p(w["rgb"]), ts=_p(ts), rays=_p(b.rays), M=M, N=N, T_thresh=1e-4, gt_rgba=_p(b.rgba),
+                               bg=_p(bg_t), bg_scalar=bg_s, lambda_rgb=lam_rgb, lambda_mask=lam_mask, grad_loss=_p(seed), grad_sigmas=_p(d_sigma),
+                               grad_rgbs=_p(d_rgb), partial=_p(w["partial"]), alpha_mode=1)
+        L.call("n2m_composite_loss_train", ctypes.addressof(head), s)
         if M > 0:
             M6 = 6 * M
             lam_eik = float(opt.lambda_eikonal) if opt.lambda_eikonal > 0 else 0.0

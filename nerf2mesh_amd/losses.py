@@ -166,7 +166,7 @@ def scatter_rows(src, idx, n):
 def sparse_depth_loss(pred_depth, gt_depth, depth_weight=None):
     """The sparse-depth term of nerf/utils.py:702-704 before its lambda: mean_n w_n (d_n m_n - g_n m_n)^2 with m = (g > 0).  (The reference
     adds the [N,1] term to its [N] loss and means the [N,N] broadcast; that mean is mean(loss) + lambda * this.)  Torch statement of the depth
-    term of n2m_composite_loss_train_depth, which the step executor runs instead."""
+    term of n2m_composite_loss_train, which the step executor runs instead."""
     m = (gt_depth > 0).to(pred_depth.dtype)
     e = (pred_depth * m - gt_depth * m) ** 2
     return (e if depth_weight is None else depth_weight * e).mean()

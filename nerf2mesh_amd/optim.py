@@ -1,4 +1,4 @@
-"""Adam + dynamic loss scaling for the whole parameter set in two launches (C ABI: n2m_adam_step / n2m_scaler_update).
+"""Adam + dynamic loss scaling for the whole parameter set in two launches (C ABI: n2m_adam_step / n2m_scaler_update_slots).
 
 Same arithmetic as `torch.optim.Adam(..., fused=True)` driven by `torch.amp.GradScaler` (main.py:221, nerf/utils.py:506,
 1187-1190): gradients are divided by the loss scale inside the update, the whole step is skipped when a gradient is not finite,
@@ -142,5 +142,7 @@ class FusedAdamAMP(torch.optim.Optimizer):
         L.call("n2m_adam_step", ctypes.addressof(desc), float(b1), float(b2), float(self.param_groups[0]["eps"]),
                L.ptr(self.scale) if self.amp else None, L.ptr(self.found_inf), L.ptr(self.bias), s)
         gf, bf, gi = self.growth
-        L.call("n2m_scaler_update_slots", L.ptr(self.scale) if self.amp else None, L.ptr(self.growth_tracker) if self.amp else None,
-               L.ptr(self.found_inf), L.ptr(self.steps), L.ptr(self.bias), participants, float(b1), float(b2), gf, bf, gi, s)
+        tail = L.ScalerTail(growth_tracker=L.ptr(self.growth_tracker) if self.amp else None, steps=L.ptr(self.steps), participants=participants,
+                            growth_factor=gf, backoff_factor=bf, growth_interval=gi)
+        L.call("n2m_scaler_update_slots", L.ptr(self.scale) if self.amp else None, L.ptr(self.found_inf), L.ptr(self.bias), float(b1), float(b2),
+               ctypes.addressof(tail), s)

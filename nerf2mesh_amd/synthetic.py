@@ -10,6 +10,7 @@
 
 Everything is plain torch and runs on CPU or on the GPU (device of the inputs).
 """
+import ctypes
 import math
 
 import torch
@@ -190,6 +191,22 @@ def random_batch(poses, images, N, generator=None, H=LEGO_HW, W=LEGO_HW, focal=L
     return o, d, images[cam, pix]
 
 
+def near_far_clamped(o, d, aabb, min_near, cam_near_far=None, cam=None):
+    """Torch statement of the batch kernel's near / far: the slab test of n2m_near_far_from_aabb, then the per-view clamp of
+    `--enable_cam_near_far` (nerf/renderer.py:689-691 with the per-ray pairs of colmap_provider.py:563-565) at the views `cam`."""
+    inv = 1.0 / d
+    lo, hi = (aabb[:3] - o) * inv, (aabb[3:] - o) * inv
+    tn, tf = torch.minimum(lo, hi).amax(-1), torch.maximum(lo, hi).amin(-1)
+    miss = tn > tf
+    big = torch.finfo(torch.float32).max
+    nears = torch.where(miss, torch.full_like(tn, big), tn.clamp(min=min_near))
+    fars = torch.where(miss, torch.full_like(tf, big), tf)
+    if cam_near_far is not None:
+        nears = torch.maximum(nears, cam_near_far[cam, 0])
+        fars = torch.minimum(fars, cam_near_far[cam, 1])
+    return nears, fars
+
+
 def batch_from_uniforms(poses, images, u, aabb, min_near, H=LEGO_HW, W=LEGO_HW, focal=LEGO_FOCAL, out=None, counter=None, cam_near_far=None):
     """A training batch from ONE tensor of uniforms u [N,6] in [0,1): view = floor(u0 V), pixel = floor(u1 H W) (N random pixels over
     random views: random_image_batch, nerf/provider.py:302-303 + nerf/utils.py:271), rays and ground truth like random_batch, near/far
@@ -205,23 +222,16 @@ def batch_from_uniforms(poses, images, u, aabb, min_near, H=LEGO_HW, W=LEGO_HW, 
             f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
             out = (f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3))
         o, d, rgba, nears, fars, noises, bg = out
-        L.call("n2m_batch_rays_cnf", L.ptr(poses), L.ptr(u), V, N, H, W, float(focal), float(focal), W / 2, H / 2, L.ptr(images), L.ptr(aabb),
-               float(min_near), L.ptr(o), L.ptr(d), L.ptr(rgba), L.ptr(nears), L.ptr(fars), L.ptr(noises), L.ptr(bg), L.ptr(counter),
-               L.ptr(cam_near_far), L.stream())
+        desc = L.BatchRays(poses=L.ptr(poses), uniforms=L.ptr(u), V=V, N=N, H=H, W=W, fx=float(focal), fy=float(focal), cx=W / 2, cy=H / 2,
+                           images=L.ptr(images), aabb=L.ptr(aabb), min_near=float(min_near), cam_near_far=L.ptr(cam_near_far), rays_o=L.ptr(o),
+                           rays_d=L.ptr(d), rgba=L.ptr(rgba), nears=L.ptr(nears), fars=L.ptr(fars), noises=L.ptr(noises), bg=L.ptr(bg),
+                           counter=L.ptr(counter))
+        L.call("n2m_batch_rays", ctypes.addressof(desc), L.stream())
         return o, d, rgba, nears, fars, noises, bg
     cam = (u[:, 0] * V).long().clamp(max=V - 1)
     pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
     o, d = rays_from_pixels(poses, cam, pix, H, W, focal)
-    inv = 1.0 / d
-    lo, hi = (aabb[:3] - o) * inv, (aabb[3:] - o) * inv
-    tn, tf = torch.minimum(lo, hi).amax(-1), torch.maximum(lo, hi).amin(-1)
-    miss = tn > tf
-    big = torch.finfo(torch.float32).max
-    nears = torch.where(miss, torch.full_like(tn, big), tn.clamp(min=min_near))
-    fars = torch.where(miss, torch.full_like(tf, big), tf)
-    if cam_near_far is not None:                       # nerf/renderer.py:689-691 with the per-ray pairs of colmap_provider.py:563-565
-        nears = torch.maximum(nears, cam_near_far[cam, 0])
-        fars = torch.minimum(fars, cam_near_far[cam, 1])
+    nears, fars = near_far_clamped(o, d, aabb, min_near, cam_near_far, cam)
     return o, d, images[cam, pix], nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous()
 
 

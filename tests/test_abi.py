@@ -103,6 +103,35 @@ def test_argument_validation_without_gpu(libpath):
         L.call("n2m_peer_copy", None, ctypes.byref(ptrs), 6, None)
     with pytest.raises(RuntimeError, match="1..8 ranks"):
         L.call("n2m_peer_reduce_slices", 16, None, 0, 8, 16, None, None, None)
+    # the step's descriptor entry points (n2m_batch_rays, n2m_composite_loss_train, n2m_scaler_update_slots): every mode of a family is one
+    # call, so the combinations no kernel is built for are refused here, before any launch (16: a stand-in for a device pointer)
+    batch = lambda **kw: ctypes.byref(L.BatchRays(**{**dict(poses=16, uniforms=16, V=2, N=4, H=3, W=3, fx=1.0, fy=1.0, aabb=16, rays_o=16, rays_d=16,
+                                                            rgba=16, nears=16, fars=16, noises=16), **kw}))
+    with pytest.raises(RuntimeError, match=r"failed \(-1\).*mutually exclusive"):
+        L.call("n2m_batch_rays", batch(images=16, bank=16, lut=16), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-2\).*both NULL"):
+        L.call("n2m_batch_rays", batch(), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-2\).*gt_depth is NULL"):
+        L.call("n2m_batch_rays", batch(bank=16, lut=16, depth_bank=16), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-2\).*depth_weight is NULL"):
+        L.call("n2m_batch_rays", batch(bank=16, lut=16, coords=16, kp_depth=16, kp_weight=16, gt_depth=16), None)
+    with pytest.raises(RuntimeError, match="scalar intrinsics"):
+        L.call("n2m_batch_rays", batch(bank=16, lut=16, coords=16, kp_depth=16, kp_weight=16, gt_depth=16, depth_weight=16, intrinsics=16), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-1\).*16-byte aligned"):
+        L.call("n2m_batch_rays", batch(bank=16, lut=16, intrinsics=20), None)
+    head = lambda **kw: ctypes.byref(L.CompositeLoss(**{**dict(rays=16, gt_rgba=16, grad_loss=16, partial=16, N=4), **kw}))
+    with pytest.raises(RuntimeError, match=r"failed \(-2\).*a ticket needs the loss output"):
+        L.call("n2m_composite_loss_train", head(ticket=16), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-3\).*density mode only"):
+        L.call("n2m_composite_loss_train", head(alpha_mode=1, gt_depth=16), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-3\).*entropy term is not built"):
+        L.call("n2m_composite_loss_train", head(alpha_mode=1, lambda_entropy=1e-3), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-2\).*both outputs or neither"):
+        L.call("n2m_composite_loss_train", head(live=16), None)
+    with pytest.raises(RuntimeError, match=r"failed \(-2\).*NULL tail"):
+        L.call("n2m_scaler_update_slots", 16, 16, 16, 0.9, 0.999, None, None)
+    with pytest.raises(RuntimeError, match=r"failed \(-1\).*need the ray count"):
+        L.call("n2m_scaler_update_slots", 16, 16, 16, 0.9, 0.999, ctypes.byref(L.ScalerTail(steps=16, loss_partial=16, n_partial=1, n_rays=0)), None)
 
 
 REFERENCE_TABLES = {   # raymarching/src/bindings.cpp:5-20, gridencoder/src/bindings.cpp:5-9, shencoder/src/bindings.cpp:5-8

@@ -70,6 +70,57 @@ def test_batch_rays_u8_equals_the_torch_statement(linear, channels, ancillary):
         assert (got[2][:, 3] == 1).all()
 
 
+@pytest.fixture(scope="module")
+def fp32_case():
+    """The fp32-image batch (synthetic.batch_from_uniforms, the benchmark's path): 300 rays over V = 3 views of 5 x 7 px -- two blocks, the
+    second partial.  The first rows of u are set by hand: 0; 1 - 2^-24, the largest uniform (at these sizes its products round to just
+    below V and H W: the last view and pixel without the clamps); 1, which only the two index clamps keep inside the bank; and the
+    neighbours of k / V on both sides, where the view index steps.  The torch statement is taken once per clamp setting."""
+    n = 300
+    g = torch.Generator().manual_seed(11)
+    u = torch.rand(n, 6, generator=g)
+    one = torch.tensor(1.0)
+    u[0, :2] = 0.0
+    u[1, :2] = 1.0 - 2.0 ** -24
+    u[2, :2] = 1.0
+    row = 3
+    for k in (1, 2):
+        edge = torch.tensor(k / V, dtype=torch.float32)
+        for x in (torch.nextafter(edge, 0 * one), edge, torch.nextafter(edge, one)):
+            u[row, 0], u[row + 1, 1] = x, x
+            row += 2
+    poses = synthetic.make_cameras(V, seed=1)
+    images = torch.rand(V, H * W, 4, generator=g)
+    near_far = synthetic.cam_near_far(poses, "lego", H, W, INTR[0])
+    aabb = torch.tensor([-1.0, -1, -1, 1, 1, 1])
+    want = {cnf: synthetic.batch_from_uniforms(poses, images, u, aabb, 0.05, H, W, INTR[0], cam_near_far=near_far if cnf else None)
+            for cnf in (False, True)}
+    cam, pix = (u[:, 0] * V).long(), (u[:, 1] * (H * W)).long()
+    assert (int(cam[1]), int(pix[1])) == (V - 1, H * W - 1) and (int(cam[2]), int(pix[2])) == (V, H * W)      # row 2 needs both clamps
+    assert cam[3:15:2].tolist() == [0, 1, 1, 1, 2, 2] and sorted(set(cam.clamp(max=V - 1).tolist())) == [0, 1, 2]
+    assert not torch.equal(want[False][3], want[True][3]) and not torch.equal(want[False][4], want[True][4])      # the per-view clamp acts
+    return dict(n=n, u=u, poses=poses, images=images, near_far=near_far, aabb=aabb, want=want)
+
+
+@pytest.mark.parametrize("with_bg", [False, True])
+@pytest.mark.parametrize("cnf", [False, True])
+def test_batch_rays_fp32_equals_the_torch_statement(fp32_case, cnf, with_bg):
+    c, n = fp32_case, fp32_case["n"]
+    f = lambda *s: torch.full(s, -7.0, dtype=torch.float32, device="cuda")
+    out = [f(n + 3, 3), f(n + 3, 3), f(n + 3, 4), f(n + 3), f(n + 3), f(n + 3), f(n + 3, 3) if with_bg else None]          # 3 guard rows each
+    counter = torch.full((1,), 5, dtype=torch.int32, device="cuda")
+    got = synthetic.batch_from_uniforms(c["poses"].cuda(), c["images"].cuda(), c["u"].cuda(), c["aabb"].cuda(), 0.05, H, W, INTR[0], out=tuple(out),
+                                        counter=counter, cam_near_far=c["near_far"].cuda() if cnf else None)
+    torch.cuda.synchronize()
+    for a, b, name in zip(got, c["want"][cnf], NAMES):
+        if a is None:
+            assert name == "bg" and not with_bg
+            continue
+        assert torch.equal(a[:n].cpu(), b), name
+        assert (a[n:] == -7.0).all(), (name, "wrote past its N rows")
+    assert int(counter) == 0
+
+
 @pytest.mark.parametrize("stride", [1, 2])
 @pytest.mark.parametrize("linear", [False, True])
 def test_capture_view_equals_the_torch_statement(stride, linear):

@@ -1,8 +1,8 @@
-"""n2m_batch_rays_sparse_u8 (csrc/capture.hip) against its torch statement (capture.batch_sparse_u8 on CPU tensors): bit for bit.
+"""n2m_batch_rays in keypoint mode (csrc/capture.hip) against its torch statement (capture.batch_sparse_u8 on CPU tensors): bit for bit.
 
 V = 3 views of 6 x 5 px with K = [1, 7, 70] keypoints (a view with a single ray, two partial workgroups), and one view with 300 keypoints
 (a full workgroup of 256 and a partial one).  The statement has no normalisation in it (rays_d is the unnormalised direction, as in
-n2m_batch_rays_u8), so the fp64 square root of the trap note on unit directions has nothing to apply to here; division and the
+the uniform mode), so the fp64 square root of the trap note on unit directions has nothing to apply to here; division and the
 slab test are correctly rounded on both sides."""
 import pytest
 import torch

@@ -1,5 +1,7 @@
-"""n2m_depth_bank_fill and n2m_batch_rays_u8_depth (csrc/capture.hip) against their torch statements (capture.dense_depth_fill and
-capture.batch_from_uniforms_u8(dense_depth=...) on CPU tensors) and against n2m_batch_rays_u8: bit for bit."""
+"""n2m_depth_bank_fill and n2m_batch_rays with a depth bank (csrc/capture.hip) against their torch statements (capture.dense_depth_fill and
+capture.batch_from_uniforms_u8(dense_depth=...) on CPU tensors) and against the same entry point without the depth bank: bit for bit."""
+import ctypes
+
 import pytest
 import torch
 
@@ -71,7 +73,7 @@ def test_batch_rays_u8_depth_equals_the_plain_kernel_and_the_statement(N, linear
         assert torch.equal(got[k][:N].cpu(), want[k]), name
         assert (got[k][N:] == -7.0).all(), (name, "wrote past its N rows")
         if k < 7:
-            assert torch.equal(got[k], plain[k]), name                    # n2m_batch_rays_u8's bits, guard rows included
+            assert torch.equal(got[k], plain[k]), name                    # the bits of the call without a depth bank, guard rows included
     if nobg:
         assert int(c1) == 0 and int(c2) == 0
     cam = (u[:, 0] * V).long().clamp(max=V - 1)
@@ -89,15 +91,17 @@ def test_batch_rays_u8_depth_refuses_a_null_bank():
     o, d, rgba, nears, fars, noises, bg, gtd = f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N, 3), f(N)
     p = L.ptr
 
-    def rc(bank, gt):
-        return L.lib().n2m_batch_rays_u8_depth(p(gpu.poses), p(u), V, N, H, W, *INTR, p(gpu.bank), bank, p(gpu.lut), p(aabb), 0.05, p(o), p(d), p(rgba),
-                                               p(nears), p(fars), p(noises), p(bg), gt, None, None, L.stream())
-    assert rc(None, p(gtd)) == L.lib().n2m_batch_rays_u8_depth(p(gpu.poses), p(u), V, N, H, W, *INTR, None, p(gpu.dense_depth), p(gpu.lut), p(aabb), 0.05,
-                                                               p(o), p(d), p(rgba), p(nears), p(fars), p(noises), p(bg), p(gtd), None, None, L.stream()) == -2
+    def desc(bank, depth_bank, gt):
+        return L.BatchRays(poses=p(gpu.poses), uniforms=p(u), V=V, N=N, H=H, W=W, fx=INTR[0], fy=INTR[1], cx=INTR[2], cy=INTR[3], bank=bank,
+                           lut=p(gpu.lut), depth_bank=depth_bank, aabb=p(aabb), min_near=0.05, rays_o=p(o), rays_d=p(d), rgba=p(rgba),
+                           nears=p(nears), fars=p(fars), noises=p(noises), bg=p(bg), gt_depth=gt)
+
+    def rc(depth_bank, gt, bank=p(gpu.bank)):
+        return L.lib().n2m_batch_rays(ctypes.byref(desc(bank, depth_bank, gt)), L.stream())
+    assert rc(None, p(gtd)) == rc(p(gpu.dense_depth), p(gtd), bank=None) == -2
     assert rc(p(gpu.dense_depth), None) == -2                             # N2M_ENULL
     torch.cuda.synchronize()
     assert (gtd == -7.0).all() and (o == -7.0).all()                       # nothing was launched
     with pytest.raises(RuntimeError, match="depth_bank is NULL"):
-        L.call("n2m_batch_rays_u8_depth", p(gpu.poses), p(u), V, N, H, W, *INTR, p(gpu.bank), None, p(gpu.lut), p(aabb), 0.05, p(o), p(d), p(rgba),
-               p(nears), p(fars), p(noises), p(bg), p(gtd), None, None, L.stream())
+        L.call("n2m_batch_rays", ctypes.byref(desc(p(gpu.bank), None, p(gtd))), L.stream())
     assert rc(p(gpu.dense_depth), p(gtd)) == 0

@@ -1,4 +1,4 @@
-"""n2m_composite_loss_train_depth: the fused loss head with the sparse-depth term (nerf/utils.py:685-705).
+"""n2m_composite_loss_train with a depth target: the fused loss head with the sparse-depth term (nerf/utils.py:685-705).
 
 Inputs: N = 70 rays whose sample counts include 0, 1, 64, 65 and 130 (the wave scan crosses a 64-sample chunk twice; the 130-sample ray keeps
 T > T_thresh to its last sample, so all three chunks carry weights and gradients), one 90-sample ray that reaches T < T_thresh on its first
@@ -8,6 +8,8 @@ Yardstick for the float comparison: the chain that existed before -- n2m_composi
 n2m_composite_rays_train_backward with grad_depth (raymarching.composite_rays_train) -- measured against float64 torch autograd of the same
 recurrence and loss in the same test; the fused kernel may show at most 4 x the chain's error (a different summation order).  Errors are
 maximum absolute differences relative to the largest float64 magnitude of the quantity.  Measured values: DESIGN 4.19."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -109,13 +111,13 @@ def _fused(case, lam_rgb, lam_mask, lam_depth, lam_ent=0.0, gtd="gtd", dw="dw", 
     lv = torch.zeros(1, device="cuda")
     depth = torch.full((N,), -7.0, device="cuda") if want_depth else None
     scale = torch.tensor(SCALE, device="cuda")
-    head = (p(c["sig"]), p(c["rgb"]), p(c["ts"]), p(c["rays"]), M, N, T_THRESH, p(c["gt"]), p(c["bg"]), 0.0, lam_rgb, lam_mask, p(scale), None, None,
-            p(d_sr[:M]), p(d_sr[M:]), p(partial), p(ticket), p(lv), None, float(lam_ent))
-    if entry == "ent":
-        L.call("n2m_composite_loss_train_ent", *head, L.stream())
-    else:
-        L.call("n2m_composite_loss_train_depth", *head, p(depth), p(None if gtd is None else c[gtd]), p(None if dw is None else c[dw]),
-               float(lam_depth), int(alpha_mode), L.stream())
+    head = L.CompositeLoss(sigmas=p(c["sig"]), rgbs=p(c["rgb"]), ts=p(c["ts"]), rays=p(c["rays"]), M=M, N=N, T_thresh=T_THRESH, gt_rgba=p(c["gt"]),
+                           bg=p(c["bg"]), lambda_rgb=lam_rgb, lambda_mask=lam_mask, grad_loss=p(scale), grad_sigmas=p(d_sr[:M]), grad_rgbs=p(d_sr[M:]),
+                           partial=p(partial), ticket=p(ticket), loss=p(lv), lambda_entropy=float(lam_ent))
+    if entry != "ent":          # + the depth fields: the same entry point's other mode
+        head.depth, head.gt_depth, head.depth_weight = p(depth), p(None if gtd is None else c[gtd]), p(None if dw is None else c[dw])
+        head.lambda_depth, head.alpha_mode = float(lam_depth), int(alpha_mode)
+    L.call("n2m_composite_loss_train", ctypes.addressof(head), L.stream())
     torch.cuda.synchronize()
     assert int(ticket) == 0
     return dict(loss=lv.item(), gs=d_sr[:M].clone(), gr=d_sr[M:].view(M, 3).clone(), depth=depth)
@@ -127,7 +129,7 @@ def _err(got, ref):
 
 @pytest.mark.parametrize("lam_ent", [0.0, 1e-3])
 def test_depth_off_is_the_entropy_head_bit_for_bit(case, lam_ent):
-    """lambda_depth = 0, and separately gt_depth = 0 everywhere: gradients and loss bit-identical to n2m_composite_loss_train_ent."""
+    """lambda_depth = 0, and separately gt_depth = 0 everywhere: gradients and loss bit-identical to the call without the depth fields."""
     want = _fused(case, LAM_RGB, LAM_MASK, 0.0, lam_ent, entry="ent")
     case["cuda"]["zero"] = torch.zeros(N, device="cuda")
     for kw in (dict(lam_depth=0.0), dict(lam_depth=LAM_DEPTH, gtd="zero"), dict(lam_depth=LAM_DEPTH, gtd=None, dw=None)):
@@ -190,5 +192,5 @@ def test_depth_output_equals_the_forward_kernel(case):
 
 
 def test_alpha_mode_with_depth_is_refused(case):
-    with pytest.raises(RuntimeError, match=r"n2m_composite_loss_train_depth failed \(-3\)"):
+    with pytest.raises(RuntimeError, match=r"n2m_composite_loss_train failed \(-3\)"):
         _fused(case, LAM_RGB, LAM_MASK, LAM_DEPTH, alpha_mode=1)

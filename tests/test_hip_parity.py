@@ -1140,7 +1140,7 @@ def _half_ulp(v):
 
 
 def test_live_first_sample_order_and_the_fill_path_of_dead_waves(be, oracle, scene):
-    """Round 5: n2m_composite_live_counts -> n2m_sample_order_live_first -> n2m_grid_backward_sample_order.
+    """Round 5: n2m_composite_loss_train's live counts -> n2m_sample_order_live_first -> n2m_grid_backward_sample_order.
     (a) The permutation is exactly: every ray's live prefix (ray order), then every ray's remaining samples (ray order).
     (b) The table backward in that order against the same call in index order: the unmerged levels (9..15) are BIT-identical (fixed-point
         sums do not depend on the order), the merged levels (0..8) agree to the rounding of the run merge (whose runs the order regroups).

@@ -1,4 +1,4 @@
-"""FusedAdamAMP (n2m_adam_step + n2m_scaler_update) against torch.optim.Adam + torch.amp.GradScaler on the same gradients."""
+"""FusedAdamAMP (n2m_adam_step + n2m_scaler_update_slots) against torch.optim.Adam + torch.amp.GradScaler on the same gradients."""
 import numpy as np
 import pytest
 
@@ -289,7 +289,7 @@ def test_state_dict_round_trip_resumes_bias_corrections_and_loss_scale():
 @pytest.mark.parametrize("overflow", [False, True])
 def test_adam_step_with_the_scaler_tail_is_the_two_launches(overflow):
     """n2m_adam_step_scaler (round 6): the optimizer pass whose last workgroup also does the scaler / step-count / loss-value bookkeeping ==
-    n2m_adam_step followed by n2m_scaler_update_slots_loss3, bit for bit, over several steps -- parameters, moments, packed rows, loss scale, growth
+    n2m_adam_step followed by n2m_scaler_update_slots, bit for bit, over several steps -- parameters, moments, packed rows, loss scale, growth
     tracker, per-slot step counts and bias corrections, the cleared found_inf flag, the loss value and its running sum; the ticket ends at zero.  A
     GradScaler overflow in the middle (overflow=True) skips the step on both sides and backs the scale off."""
     import ctypes
@@ -342,8 +342,9 @@ def test_adam_step_with_the_scaler_tail_is_the_two_launches(overflow):
         # (a) two launches
         da = desc_of(a, grads[:n])
         L.call("n2m_adam_step", ctypes.addressof(da), 0.9, 0.999, 1e-15, p(a["scale"]), p(a["found_inf"]), p(a["bias"]), L.stream())
-        L.call("n2m_scaler_update_slots_loss3", p(a["scale"]), p(a["growth"]), p(a["found_inf"]), p(a["steps"]), p(a["bias"]), participants, 0.9, 0.999,
-               *growth, p(part), n_partial, n_rays, p(a["loss"]), p(a["loss_sum"]), p(ex), n_extra, 0.25, p(ex2), n_extra2, 0.125, L.stream())
+        tail_a = L.ScalerTail(p(a["growth"]), p(a["steps"]), participants, *growth, p(part), n_partial, n_rays, p(a["loss"]), p(a["loss_sum"]), p(ex),
+                              n_extra, 0.25, p(ex2), n_extra2, 0.125, None)
+        L.call("n2m_scaler_update_slots", p(a["scale"]), p(a["found_inf"]), p(a["bias"]), 0.9, 0.999, ctypes.addressof(tail_a), L.stream())
         # (b) one launch
         db = desc_of(b, grads[:n])
         tail = L.ScalerTail(p(b["growth"]), p(b["steps"]), participants, *growth, p(part), n_partial, n_rays, p(b["loss"]), p(b["loss_sum"]), p(ex), n_extra,

@@ -1,5 +1,7 @@
-"""n2m_batch_rays_u8_pv (csrc/capture.hip) and the per-view paths of n2m_capture_view / n2m_batch_rays_sparse_u8 against their torch statements
+"""n2m_batch_rays with an intrinsics table (csrc/capture.hip) and the per-view paths of n2m_capture_view / the keypoint batch against their torch statements
 in nerf2mesh_amd/capture.py (taken on the CPU), and -- with a table of EQUAL rows -- against the shared-intrinsics kernels: bit for bit."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -98,7 +100,8 @@ def test_batch_rays_u8_pv_equals_the_torch_statement(linear, channels, ancillary
 @pytest.mark.parametrize("dense", [False, True])
 @pytest.mark.parametrize("ancillary", ["cnf_nobg_counter", "nocnf_bg"])
 def test_equal_rows_give_the_bits_of_the_shared_kernels(ancillary, dense):
-    """per_view=True with equal rows: n2m_batch_rays_u8_pv against n2m_batch_rays_u8 / n2m_batch_rays_u8_depth on the same set."""
+    """per_view=True with equal rows: n2m_batch_rays with the table against the same entry point with the four scalars, with and without
+    the depth bank, on the same set."""
     cnf = ancillary == "cnf_nobg_counter"
     same = np.tile(ROWS[1], (V, 1))
     _, table = _captures(4, False, cnf, rows=same, per_view=True)
@@ -123,20 +126,21 @@ def test_one_of_the_two_depth_pointers_missing_is_enull():
     o, d, rgba, a, b, c, gtd = f(N, 3), f(N, 3), f(N, 4), f(N), f(N), f(N), f(N)
     p = L.ptr
 
-    def args(bank, gt):
-        return (p(gpu.poses), p(u), V, N, H, W, p(gpu.intrinsics), p(gpu.bank), bank, p(gpu.lut), p(aabb), 0.05, p(o), p(d), p(rgba), p(a), p(b), p(c),
-                None, gt, None, None, L.stream())
+    def desc(depth_bank, gt, intrinsics=p(gpu.intrinsics)):
+        return ctypes.byref(L.BatchRays(
+            poses=p(gpu.poses), uniforms=p(u), V=V, N=N, H=H, W=W, intrinsics=intrinsics, bank=p(gpu.bank), lut=p(gpu.lut), depth_bank=depth_bank,
+            aabb=p(aabb), min_near=0.05, rays_o=p(o), rays_d=p(d), rgba=p(rgba), nears=p(a), fars=p(b), noises=p(c), gt_depth=gt))
     for bank, gt, missing in ((p(gpu.dense_depth), None, "gt_depth"), (None, p(gtd), "depth_bank")):
-        assert L.lib().n2m_batch_rays_u8_pv(*args(bank, gt)) == -2                     # N2M_ENULL
-        with pytest.raises(RuntimeError, match=rf"n2m_batch_rays_u8_pv failed \(-2\).*{missing} is NULL"):
-            L.call("n2m_batch_rays_u8_pv", *args(bank, gt))
-    L.call("n2m_batch_rays_u8_pv", *args(None, None))                                  # both NULL: the plain batch
-    L.call("n2m_batch_rays_u8_pv", *args(p(gpu.dense_depth), p(gtd)))
+        assert L.lib().n2m_batch_rays(desc(bank, gt), L.stream()) == -2               # N2M_ENULL
+        with pytest.raises(RuntimeError, match=rf"n2m_batch_rays failed \(-2\).*{missing} is NULL"):
+            L.call("n2m_batch_rays", desc(bank, gt), L.stream())
+    L.call("n2m_batch_rays", desc(None, None), L.stream())                             # both NULL: the plain batch
+    L.call("n2m_batch_rays", desc(p(gpu.dense_depth), p(gtd)), L.stream())
     torch.cuda.synchronize()
     with pytest.raises(RuntimeError, match="16-byte aligned"):
-        L.call("n2m_batch_rays_u8_pv", *(args(None, None)[:6] + (p(gpu.intrinsics) + 4,) + args(None, None)[7:]))
-    with pytest.raises(RuntimeError, match="intrinsics is NULL"):
-        L.call("n2m_batch_rays_u8_pv", *(args(None, None)[:6] + (None,) + args(None, None)[7:]))
+        L.call("n2m_batch_rays", desc(None, None, p(gpu.intrinsics) + 4), L.stream())
+    with pytest.raises(RuntimeError, match="intrinsics is NULL"):                      # ... and no scalars in their place
+        L.call("n2m_batch_rays", desc(None, None, None), L.stream())
 
 
 @pytest.mark.parametrize("ssaa", [0, 2])

@@ -1,5 +1,7 @@
 """GPU parity of the fused training-step helpers against the torch graph the reference builds (nerf/utils.py:658-683,
 nerf/renderer.py:747).  fp32 tolerance: the kernel sums in a different (fixed) order than torch's reductions."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -90,16 +92,25 @@ def test_fused_composite_loss_equals_the_four_kernel_chain(bg_kind):
     ticket = torch.zeros(1, dtype=torch.int32, device=dev)
     lv, lsum = torch.zeros(1, device=dev), torch.full((1,), 2.0, device=dev)
     bg_t = bg if torch.is_tensor(bg) else None
-    # + the optional live counts (round 5, n2m_composite_live_counts): per ray the samples up to and including the early stop
+    # + the optional live counts (round 5; descriptor fields live / block_live): per ray the samples up to and including the early stop
     live = torch.full((N,), -7, dtype=torch.int32, device=dev)
     block_live = torch.full(((N + 15) // 16,), -7, dtype=torch.int32, device=dev)
-    L.call("n2m_composite_live_counts", L.ptr(live), L.ptr(block_live))
-    try:
-        L.call("n2m_composite_loss_train", L.ptr(sig.detach()), L.ptr(rgb.detach()), L.ptr(ts), L.ptr(rays), M, N, 1e-4, L.ptr(gt), L.ptr(bg_t),
-               1.0 if bg_t is None else 0.0, 1.0, 0.1, L.ptr(scale), L.ptr(out_ws), L.ptr(out_im), L.ptr(d_sr[:M]), L.ptr(d_sr[M:]), L.ptr(partial),
-               L.ptr(ticket), L.ptr(lv), L.ptr(lsum), L.stream())
-    finally:
-        L.call("n2m_composite_live_counts", None, None)
+    head = L.CompositeLoss(sigmas=L.ptr(sig.detach()), rgbs=L.ptr(rgb.detach()), ts=L.ptr(ts), rays=L.ptr(rays), M=M, N=N, T_thresh=1e-4,
+                           gt_rgba=L.ptr(gt), bg=L.ptr(bg_t), bg_scalar=1.0 if bg_t is None else 0.0, lambda_rgb=1.0, lambda_mask=0.1,
+                           grad_loss=L.ptr(scale), weights_sum=L.ptr(out_ws), image=L.ptr(out_im), grad_sigmas=L.ptr(d_sr[:M]),
+                           grad_rgbs=L.ptr(d_sr[M:]), partial=L.ptr(partial), ticket=L.ptr(ticket), loss=L.ptr(lv), loss_sum=L.ptr(lsum),
+                           live=L.ptr(live), block_live=L.ptr(block_live))
+    L.call("n2m_composite_loss_train", ctypes.addressof(head), L.stream())
+    # ... and a call right behind it that asks for none leaves two poison-filled buffers alone: nothing sticky is left behind
+    live_snapshot, block_snapshot = live.clone(), block_live.clone()
+    live.fill_(-7); block_live.fill_(-7)
+    d_sr2, lv2 = torch.empty(4 * M, device=dev), torch.zeros(1, device=dev)
+    head.live, head.block_live, head.loss_sum = None, None, None
+    head.grad_sigmas, head.grad_rgbs, head.loss, head.weights_sum, head.image = L.ptr(d_sr2[:M]), L.ptr(d_sr2[M:]), L.ptr(lv2), None, None
+    L.call("n2m_composite_loss_train", ctypes.addressof(head), L.stream())
+    assert bool((live == -7).all()) and bool((block_live == -7).all())
+    assert torch.equal(d_sr2, d_sr) and lv2.item() == lv.item() and int(ticket) == 0
+    live, block_live = live_snapshot, block_snapshot
     assert torch.equal(out_ws, ws.detach()) and torch.equal(out_im, im.detach())
     assert torch.equal(d_sr[:M], sig.grad) and torch.equal(d_sr[M:].view(M, 3), rgb.grad)
     np.testing.assert_allclose(lv.item(), loss.item(), rtol=5e-6)
@@ -122,7 +133,7 @@ def test_fused_composite_loss_equals_the_four_kernel_chain(bg_kind):
 
 
 def test_fused_composite_loss_with_the_entropy_regulariser():
-    """n2m_composite_loss_train_ent == the autograd statement of config 4's loss (nerf/utils.py:728-733 on top of the rgb + mask loss):
+    """n2m_composite_loss_train with lambda_entropy > 0 == the autograd statement of config 4's loss (nerf/utils.py:728-733 on top of the rgb + mask loss):
     the entropy of the sample weights reaches composite_rays_train's backward as grad_weights (the per-sample factor the reference kernel
     applies at raymarching.cu:676), the entropy of weights_sum as an extra grad_weights_sum.  Gradients to 2e-5 of their maximum (log2
     spelled once instead of twice, fp32), loss value to 1e-5; lambda = 0 reproduces the plain kernel bit for bit."""
@@ -152,8 +163,10 @@ def test_fused_composite_loss_with_the_entropy_regulariser():
     def fused(lam_):
         d_sr = torch.empty(4 * M, device=dev)
         partial = torch.empty((N + 15) // 16, device=dev)
-        L.call("n2m_composite_loss_train_ent", L.ptr(sig.detach()), L.ptr(rgb.detach()), L.ptr(ts), L.ptr(rays), M, N, 1e-4, L.ptr(gt), L.ptr(bg),
-               0.0, 1.0, 0.1, L.ptr(scale), None, None, L.ptr(d_sr[:M]), L.ptr(d_sr[M:]), L.ptr(partial), None, None, None, float(lam_), L.stream())
+        head = L.CompositeLoss(sigmas=L.ptr(sig.detach()), rgbs=L.ptr(rgb.detach()), ts=L.ptr(ts), rays=L.ptr(rays), M=M, N=N, T_thresh=1e-4,
+                               gt_rgba=L.ptr(gt), bg=L.ptr(bg), lambda_rgb=1.0, lambda_mask=0.1, grad_loss=L.ptr(scale), grad_sigmas=L.ptr(d_sr[:M]),
+                               grad_rgbs=L.ptr(d_sr[M:]), partial=L.ptr(partial), lambda_entropy=float(lam_))
+        L.call("n2m_composite_loss_train", ctypes.addressof(head), L.stream())
         return d_sr[:M].clone(), d_sr[M:].view(M, 3).clone(), float(partial.double().sum() / N)
     gs, gr, lv = fused(lam)
     assert torch.equal(gr, rgb.grad)                                               # the colour gradient does not see the term
@@ -165,8 +178,10 @@ def test_fused_composite_loss_with_the_entropy_regulariser():
     assert (gs0 - gs).abs().max().item() > 1e-3 * gs.abs().max().item()
     d_sr = torch.empty(4 * M, device=dev)
     partial = torch.empty((N + 15) // 16, device=dev)
-    L.call("n2m_composite_loss_train", L.ptr(sig.detach()), L.ptr(rgb.detach()), L.ptr(ts), L.ptr(rays), M, N, 1e-4, L.ptr(gt), L.ptr(bg),
-           0.0, 1.0, 0.1, L.ptr(scale), None, None, L.ptr(d_sr[:M]), L.ptr(d_sr[M:]), L.ptr(partial), None, None, None, L.stream())
+    head = L.CompositeLoss(sigmas=L.ptr(sig.detach()), rgbs=L.ptr(rgb.detach()), ts=L.ptr(ts), rays=L.ptr(rays), M=M, N=N, T_thresh=1e-4,
+                           gt_rgba=L.ptr(gt), bg=L.ptr(bg), lambda_rgb=1.0, lambda_mask=0.1, grad_loss=L.ptr(scale), grad_sigmas=L.ptr(d_sr[:M]),
+                           grad_rgbs=L.ptr(d_sr[M:]), partial=L.ptr(partial))          # a descriptor that never heard of the term
+    L.call("n2m_composite_loss_train", ctypes.addressof(head), L.stream())
     assert torch.equal(d_sr[:M], gs0) and torch.equal(d_sr[M:].view(M, 3), gr0)
 
 
