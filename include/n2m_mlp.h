@@ -81,6 +81,32 @@ int n2m_field_backward_train(const float* xyz, const float* dirs, const float* h
                              float* d_w_spec1, float* found_inf, float spec_reg, const float* seed, void* stream);
 uint32_t n2m_field_spec_partials(void);      /* slots the forward writes into spec_sq_partial (512) */
 
+/* ---- the second stage of the backward's weight-gradient reduction, on its own
+ * The backward's workgroups leave their 7 648 sums as rows of a scratch; a second launch adds the rows up in a fixed order (sixteen
+ * interleaved slices per element, then slice 0..15), ACCUMULATES the sums into the seven d_w tensors and raises found_inf on a non-finite
+ * one.  Nothing but the optimizer reads those outputs, so the sum does not have to be a launch of its own behind the backward:
+ *   n2m_field_backward_defer_dw(&d)   the NEXT n2m_field_backward[_train] of this thread (one-shot; NULL disarms) skips that launch
+ *                                     and describes it in d: partial rows (library-owned scratch of the call's stream, valid until the next
+ *                                     field backward on that stream), row count, the tensors and which of them take part (mask bit i = tensor i
+ *                                     in the order sigma0 sigma1 color0 color1 color2 spec0 spec1).  d is zeroed here; d.partial stays NULL
+ *                                     when the call had nothing to sum (M == 0).  Not for the *_ind forms.
+ *   n2m_field_dw_sum(&d, stream)      the stand-alone launch: exactly what the backward would have launched;
+ *   n2m_grid_backward_dw_rider(&d, &carried)   the same sum as 120 extra workgroups ("riders") at the end of the grid of the accumulate kernel
+ *                                     of the NEXT n2m_grid_encode_backward_binned_pair* call of this thread (one-shot; NULL disarms): the rows are
+ *                                     complete before that kernel starts and only the optimizer reads the sums, so no workgroup waits for
+ *                                     another.  Same body, same order, same bits.  *carried (host int, written during that call) becomes 1 when
+ *                                     the call took the sum along -- the partition-major path with both tables in one accumulate launch -- and
+ *                                     stays as it was otherwise: the caller then runs n2m_field_dw_sum itself. */
+typedef struct N2mDwSum {
+    const float* partial;
+    uint32_t n_rows, mask;
+    float* dw[7];
+    float* found_inf;
+} N2mDwSum;
+int n2m_field_backward_defer_dw(N2mDwSum* out);
+int n2m_field_dw_sum(const N2mDwSum* d, void* stream);
+int n2m_grid_backward_dw_rider(const N2mDwSum* d, int* carried);
+
 /* ---- per-image appearance codes (--ind_dim of the reference, nerf/renderer.py:356,703,850; nerf/network.py:159-166)
  * color_net's layer 0 then reads [x(3) | h2(32) | code(D)]: w_color0 is the parameter as nn.Linear stores it, row-major [64, 35 + D] (no
  * repacked copy), codes is individual_codes [R, D] f32 and sample_view [M] int32 names the row of every sample (values are clamped to

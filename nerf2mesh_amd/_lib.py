@@ -152,6 +152,9 @@ SIGNATURES = {
     "n2m_field_forward_train": [_vp] * 11 + [_u32, _int, _int] + [_vp] * 5,
     "n2m_field_backward_train": [_vp] * 11 + [_u32, _int, _int] + [_vp] * 13 + [_f32, _vp, _vp],
     "n2m_field_spec_partials": [],
+    "n2m_field_backward_defer_dw": [_vp],
+    "n2m_field_dw_sum": [_vp, _vp],
+    "n2m_grid_backward_dw_rider": [_vp, _vp],
     "n2m_field_ind_max_dim": [],
     "n2m_field_ind_workspace_bytes": [_u32, _u32],
     "n2m_field_sample_views": [_vp, _vp, _u32, _u32, _vp, _vp],
@@ -221,6 +224,11 @@ class ScalerTail(ctypes.Structure):
                 ("growth_interval", _f32), ("loss_partial", _vp), ("n_partial", _u32), ("n_rays", _u32), ("loss", _vp), ("loss_sum", _vp),
                 ("extra_partial", _vp), ("n_extra", _u32), ("extra_scale", _f32), ("extra2_partial", _vp), ("n_extra2", _u32),
                 ("extra2_scale", _f32), ("ticket", _vp)]
+
+
+class DwSum(ctypes.Structure):
+    """N2mDwSum of include/n2m_mlp.h."""
+    _fields_ = [("partial", _vp), ("n_rows", _u32), ("mask", _u32), ("dw", _vp * 7), ("found_inf", _vp)]
 
 
 class BatchRays(ctypes.Structure):

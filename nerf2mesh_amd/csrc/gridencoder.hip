@@ -18,6 +18,8 @@
 
 #include "n2m_common.hpp"
 #include "../../include/n2m_peer.h"
+#include "../../include/n2m_mlp.h"      /* N2mDwSum (n2m_grid_backward_dw_rider) */
+#include "n2m_dw_sum.hpp"
 
 namespace {
 
@@ -3287,6 +3289,36 @@ pm_accumulate_both_kernel(float* __restrict__ table1, _Float16* __restrict__ tab
                                                     cursors, ovf_cursor, log_rel, log_v2, ovf_key, ovf_v2, slots2, tickets2, found_inf, overwrite, dbg, bound2, prk, prt2);
 }
 
+// pm_accumulate_both_kernel + RIDER workgroups: the last kDwSumBlocks workgroups of the grid do not touch the tables; they run the second stage of
+// the field backward's weight-gradient reduction (dw_sum_body, n2m_dw_sum.hpp: what dw_finalize_kernel does as a launch of its own between the
+// field backward and the fill).  Its inputs -- the partial rows -- are complete before this kernel starts and its outputs -- the d_w tensors,
+// found_inf raised -- are read by the optimizer pass only, so nobody waits for anybody: no ticket, no fence.  The riders sit at the END of the
+// grid: the accumulate's own workgroups keep their indices (item = blockIdx.x, stride nb1 / nb2 as before) and are dispatched first; the riders
+// fill CUs in the kernel's tail.  They branch off before the accumulate touches LDS and use 4 KB of its dynamic allocation.  A kernel of its
+// own, not a flag of pm_accumulate_both_kernel: every other caller launches the kernel it always did.
+struct DwRider { const float* part; uint32_t n_rows, mask; DwOut o; float* found_inf; };
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8)))
+pm_accumulate_both_dw_kernel(float* __restrict__ table1, _Float16* __restrict__ table2, PmBoth pb, PmPlan pm, LevelTable lv, uint32_t gridtype, bool align_corners,
+                             const uint32_t* __restrict__ level_max, const uint32_t* __restrict__ cursors, const uint32_t* __restrict__ ovf_cursor,
+                             const uint16_t* __restrict__ log_rel, const uint32_t* __restrict__ log_v1, const uint32_t* __restrict__ log_v2,
+                             const uint32_t* __restrict__ ovf_key, const uint32_t* __restrict__ ovf_v1, const uint32_t* __restrict__ ovf_v2,
+                             unsigned long long* __restrict__ slots1, unsigned long long* __restrict__ slots2, uint32_t* __restrict__ tickets1,
+                             uint32_t* __restrict__ tickets2, float* __restrict__ found_inf, bool overwrite, uint32_t dbg, float bound1, float bound2, uint32_t nb1,
+                             uint32_t nb2, PeerRouteK prk, PeerRouteT prt1, PeerRouteT prt2, DwRider dr) {
+    static_assert(kPairP * 16u >= 16u * 64u * sizeof(float), "the rider's 4 KB come out of the accumulate's dynamic LDS");
+    if (blockIdx.x >= nb1 + nb2) {
+        extern __shared__ __attribute__((aligned(16))) unsigned long long bin_acc[];
+        dw_sum_body(reinterpret_cast<float(*)[64]>(bin_acc), blockIdx.x - (nb1 + nb2), dr.part, dr.n_rows, dr.o, dr.mask, dr.found_inf);
+        return;
+    }
+    if (blockIdx.x < nb1)
+        pm_accumulate_items<float, 1, kPairP, 2>(blockIdx.x, nb1, table1, pb.plan1, pm, pb.sp1, lv, gridtype, align_corners, level_max, cursors, ovf_cursor, log_rel,
+                                                 log_v1, ovf_key, ovf_v1, slots1, tickets1, found_inf, overwrite, dbg, bound1, prk, prt1);
+    else
+        pm_accumulate_items<_Float16, 2, kPairP, 1>(blockIdx.x - nb1, nb2, table2, pb.plan2, pm, pb.sp2, lv, gridtype, align_corners, level_max + kMaxLevels,
+                                                    cursors, ovf_cursor, log_rel, log_v2, ovf_key, ovf_v2, slots2, tickets2, found_inf, overwrite, dbg, bound2, prk, prt2);
+}
+
 // grad_inputs[b,d] = sum_{l,c} grad[l,b,c] * dy_dx[b,l,d,c]; accumulates in T like the reference (:357-365)
 template <typename T, uint32_t D, uint32_t C>
 __global__ void grid_input_backward_kernel(const T* __restrict__ grad, const T* __restrict__ dy_dx, T* __restrict__ grad_inputs,
@@ -3656,6 +3688,21 @@ extern "C" int n2m_grid_backward_tv_corners(const float* corners) {
     return 0;
 }
 
+// The field backward's weight-gradient sum the NEXT table backward of this thread takes along as rider workgroups of its accumulate kernel
+// (one-shot, n2m_grid_backward_dw_rider; pm_accumulate_both_dw_kernel).  *carried is set when a launch took it.
+static thread_local N2mDwSum g_dw_rider{};
+static thread_local int* g_dw_rider_carried = nullptr;
+extern "C" int n2m_grid_backward_dw_rider(const N2mDwSum* d, int* carried) {
+    if (d == nullptr) { g_dw_rider = N2mDwSum{}; g_dw_rider_carried = nullptr; return 0; }
+    N2M_REQUIRE(d->partial != nullptr && carried != nullptr, N2M_ENULL, "n2m_grid_backward_dw_rider: NULL partial rows / carried");
+    N2M_REQUIRE(d->n_rows >= 1 && (d->mask & ~0x7Fu) == 0, N2M_EINVAL, "n2m_grid_backward_dw_rider: no rows, or a mask beyond seven tensors");
+    for (int i = 0; i < 7; ++i)
+        N2M_REQUIRE(!((d->mask >> i) & 1u) || d->dw[i] != nullptr, N2M_ENULL, "n2m_grid_backward_dw_rider: tensor %d is in the mask and NULL", i);
+    g_dw_rider = *d;
+    g_dw_rider_carried = carried;
+    return 0;
+}
+
 static unsigned int g_fill_dbg_host = 0u;          // host mirror of g_fill_timing_on (n2m_debug_fill_times): a non-zero word selects the EX kernels
 static thread_local const uint32_t* g_sample_order = nullptr;
 extern "C" int n2m_grid_backward_sample_order(const uint32_t* perm) {
@@ -3716,6 +3763,7 @@ int launch_binned_pair_pm(const float* grad1, const _Float16* grad2, const float
         (void)hipFuncSetAttribute((const void*)pm_accumulate_kernel<float, 1, kPairP, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kPairP * 16));
         (void)hipFuncSetAttribute((const void*)pm_accumulate_kernel<_Float16, 2, kPairP, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kPairP * 16));
         (void)hipFuncSetAttribute((const void*)pm_accumulate_both_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kPairP * 16));
+        (void)hipFuncSetAttribute((const void*)pm_accumulate_both_dw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kPairP * 16));
         attr_set = true;
     }
     const uint32_t TS = pm_tile_samples();
@@ -3908,6 +3956,18 @@ int launch_binned_pair_pm(const float* grad1, const _Float16* grad2, const float
         static const bool one_launch = getenv("N2M_PM_ACC_SPLIT") == nullptr;
         if (both && has2 && one_launch) {
             PmBoth pb{plan1, plan2, sp1, sp2};
+            if (g_dw_rider.partial != nullptr && acc_dbg == 0u) {      // one-shot: this launch carries the field backward's dW sum
+                DwRider dr{g_dw_rider.partial, g_dw_rider.n_rows, g_dw_rider.mask, DwOut{}, g_dw_rider.found_inf};
+                for (int i = 0; i < 7; ++i) dr.o.dw[i] = g_dw_rider.dw[i];
+                N2M_LAUNCH(pm_accumulate_both_dw_kernel, nb1 + nb2 + kDwSumBlocks, 1024, kPairP * 16, s, table1, table2, pb, pl.pm, lv, gridtype, align, level_max, cursors,
+                           ovf_cursor, log_rel, log_v1, log_v2, ovf_key, ovf_v1, ovf_v2, slots, slots_t2, tickets, tickets2, found_inf, ow, acc_dbg,
+                           3.0e38f / odiv, 65504.0f / odiv, nb1, nb2, prk, prt1, prt2, dr);
+                N2M_CHECK_LAUNCH();
+                *g_dw_rider_carried = 1;
+                g_dw_rider = N2mDwSum{};
+                g_dw_rider_carried = nullptr;
+                continue;
+            }
             N2M_LAUNCH(pm_accumulate_both_kernel, nb1 + nb2, 1024, kPairP * 16, s, table1, table2, pb, pl.pm, lv, gridtype, align, level_max, cursors, ovf_cursor, log_rel, log_v1,
                                                                            log_v2, ovf_key, ovf_v1, ovf_v2, slots, slots_t2, tickets, tickets2, found_inf, ow, acc_dbg,
                                                                            3.0e38f / odiv, 65504.0f / odiv, nb1, prk, prt1, prt2);

@@ -24,6 +24,7 @@
 
 #include "n2m_common.hpp"
 #include "../../include/n2m_mlp.h"
+#include "n2m_dw_sum.hpp"
 
 namespace {
 
@@ -641,9 +642,7 @@ __device__ void dw_flush(float* __restrict__ dW, const float* stage, int in_pad,
 // Now a workgroup stores its sums as one row of a [workgroups][7 648] scratch (plain coalesced stores) and this kernel adds the rows
 // up in a fixed order (sixteen interleaved slices per element, then slice 0..15): ~2 M L2-resident loads, no atomics, and the result no
 // longer depends on the order in which workgroups finish.
-constexpr int kDwOff[8] = {0, 608, 640, 2880, 6976, 7360, 7552, 7648};      // sigma0 sigma1 color0 color1 color2 spec0 spec1
-constexpr int kDwTotal = 7648;
-struct DwOut { float* dw[7]; };
+// (kDwOff, kDwTotal, DwOut and the body of this kernel: n2m_dw_sum.hpp -- the table backward's accumulate can carry the same sum)
 // accumulator tile of ONE consumer wave -> its own LDS copy (plain stores: four waves adding into one copy with ds_add_f32 measured
 // 62 us per launch for 224 instructions per lane -- the LDS float atomic is that slow), then the four copies are summed in wave order
 template <int MB, int NB>
@@ -668,36 +667,7 @@ __device__ void dw_store_partial(float* __restrict__ part, const float* stage, i
 }
 __global__ void __launch_bounds__(1024) dw_finalize_kernel(const float* __restrict__ part, uint32_t n_rows, DwOut o, uint32_t mask, float* found_inf) {
     __shared__ float sm[16][64];
-    const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + lane;
-    int mat = 0;
-#pragma unroll
-    for (int i = 1; i < 7; ++i) mat += e >= kDwOff[i] ? 1 : 0;
-    const bool live = e < kDwTotal && ((mask >> mat) & 1u);
-    float acc = 0.f;
-    if (live) {
-        // rows slice, slice + 16, ...: <= 16 per thread for 256 workgroups, all loads of a thread in flight together
-        float v[16];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const uint32_t w = (uint32_t)slice + 16u * i;
-            v[i] = w < n_rows ? part[(size_t)w * kDwTotal + e] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc += v[i];
-        for (uint32_t w = (uint32_t)slice + 256u; w < n_rows; w += 16u) acc += part[(size_t)w * kDwTotal + e];     // larger grids (not used today)
-    }
-    sm[slice][lane] = acc;
-    __syncthreads();
-    if (slice == 0 && live) {
-        float v = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) v += sm[i][lane];
-        if (v != 0.f) {
-            o.dw[mat][e - kDwOff[mat]] += v;
-            if (!(fabsf(v) <= 3.0e38f) && found_inf) *found_inf = 1.0f;
-        }
-    }
+    dw_sum_body(sm, blockIdx.x, part, n_rows, o, mask, found_inf);
 }
 
 template <bool DO_DENSITY, bool DO_COLOR>
@@ -1406,6 +1376,31 @@ extern "C" int n2m_field_forward_train(const float* xyz, const float* dirs, cons
 }
 extern "C" uint32_t n2m_field_spec_partials(void) { return (uint32_t)kSpecPartials; }
 
+// The NEXT plain field backward of this thread leaves the second stage of its weight-gradient reduction to the caller and describes it in
+// *out (one-shot; n2m_field_backward_defer_dw).  The IND backward keeps its own finalize: it is not covered.
+static thread_local N2mDwSum* g_defer_dw = nullptr;
+extern "C" int n2m_field_backward_defer_dw(N2mDwSum* out) {
+    g_defer_dw = out;
+    if (out) *out = N2mDwSum{};
+    return 0;
+}
+static int check_dw_sum(const char* fn, const N2mDwSum* d) {
+    N2M_REQUIRE(d != nullptr && d->partial != nullptr, N2M_ENULL, "%s: NULL description / partial rows", fn);
+    N2M_REQUIRE(d->n_rows >= 1, N2M_EINVAL, "%s: no partial rows", fn);
+    N2M_REQUIRE((d->mask & ~0x7Fu) == 0, N2M_EINVAL, "%s: mask names seven tensors", fn);
+    for (int i = 0; i < 7; ++i)
+        N2M_REQUIRE(!((d->mask >> i) & 1u) || d->dw[i] != nullptr, N2M_ENULL, "%s: tensor %d is in the mask and NULL", fn, i);
+    return 0;
+}
+extern "C" int n2m_field_dw_sum(const N2mDwSum* d, void* stream) {
+    if (int rc = check_dw_sum("field_dw_sum", d)) return rc;
+    DwOut o;
+    for (int i = 0; i < 7; ++i) o.dw[i] = d->dw[i];
+    N2M_LAUNCH(dw_finalize_kernel, kDwSumBlocks, 1024, 0, (hipStream_t)stream, d->partial, d->n_rows, o, d->mask, d->found_inf);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
+
 static int field_backward_impl(const float* xyz, const float* dirs, const float* h1, const void* h2, const float* w_sigma0,
                                   const float* w_sigma1, const float* w_color0, const float* w_color1, const float* w_color2,
                                   const float* w_spec0, const float* w_spec1, uint32_t M, int shading, int normalize_dirs, const float* d_sigma,
@@ -1486,10 +1481,18 @@ static int field_backward_impl(const float* xyz, const float* dirs, const float*
         DwOut o;
         for (int i = 0; i < 7; ++i) o.dw[i] = dw[i];
         const uint32_t mask = (density ? 0x03u : 0u) | (color ? 0x1Cu : 0u) | (color && shading != 0 ? 0x60u : 0u);
+        if (g_defer_dw) {      // the caller runs the sum itself (n2m_field_dw_sum, or as rider workgroups of the table backward's accumulate)
+            N2mDwSum* d = g_defer_dw;
+            g_defer_dw = nullptr;
+            d->partial = part; d->n_rows = grid; d->mask = mask; d->found_inf = found_inf;
+            for (int i = 0; i < 7; ++i) d->dw[i] = dw[i];
+            return 0;
+        }
         if (!(dbg & 2)) N2M_LAUNCH(dw_finalize_kernel, (kDwTotal + 63) / 64, 1024, 0, s, part, grid, o, mask, found_inf);
         N2M_CHECK_LAUNCH();
         return 0;
     }
+    N2M_REQUIRE(g_defer_dw == nullptr, N2M_EUNSUPPORTED, "field_backward: the one-wave kernel (N2M_FIELD_BWD_SINGLE) has no second stage to defer");
     const size_t smem = (size_t)BWD_HALVES * 2;
     if (color && density) N2M_LAUNCH((field_backward_kernel<true, true>), persistent_grid(M), 256, smem, s, a);
     else if (color) N2M_LAUNCH((field_backward_kernel<false, true>), persistent_grid(M), 256, smem, s, a);

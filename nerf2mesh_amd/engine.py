@@ -10,7 +10,8 @@ streams, the random generators and torch.distributed -- and does the rest itself
         -> n2m_march_rays_train_fused (one march: counts + recorded chunks, replay) -> count to pinned memory + event
   step (main stream, batch i):  n2m_grid_encode_forward_packed[_tvterms: one GPU, the lookup also leaves the backward's TV terms] ->
         n2m_field_forward -> n2m_composite_loss_train (compositing, loss head,
-        both backward passes) -> n2m_field_backward -> n2m_grid_encode_backward_binned_pair (+TV) / ..._pair_tvt -> [world > 1: SUM all-reduce of the
+        both backward passes) -> n2m_field_backward [one GPU: the second stage of its dW reduction deferred and carried by the table backward's
+        accumulate kernel as rider workgroups] -> n2m_grid_encode_backward_binned_pair (+TV) / ..._pair_tvt -> [world > 1: SUM all-reduce of the
         fixed gradient buffers, fine levels first] -> n2m_adam_step -> n2m_scaler_update_slots
 
 Same kernels, same arguments, same random draws in the same order as Stage0Trainer: the two produce the same parameters
@@ -187,6 +188,13 @@ class Stage0Engine:
         # in front of the next lookup).  Identical bits (tests/test_optim.py, tests/test_adam_tail.py) -- but the optimizer pass takes 136 us instead of 93
         # in the kernel that also holds the bookkeeping code, whatever the arrival scheme: step 0.540 -> 0.563 ms.
         self.adam_tail = os.environ.get("N2M_ADAM_TAIL", "0") == "1" and world_size == 1
+        # [the default on one GPU, A/B: N2M_RIDERS=0]  Rider workgroups: the second stage of the field backward's weight-gradient reduction (a launch of
+        # its own between the field backward and the fill, 5 us on the main stream's serial chain) runs as 120 extra workgroups at the end of the
+        # accumulate kernel's grid (n2m_field_backward_defer_dw + n2m_grid_backward_dw_rider).  Its inputs are complete when the field backward ends
+        # and only the optimizer pass reads its outputs, so nobody waits for anybody; same body, same order, same bits.  Not with SDF, several
+        # ranks, --ind_dim or the depth-supervised heads: they keep the separate launch.  (The scaler update was the other candidate and is NOT a
+        # rider: the lookup that leaves the TV terms reads the loss scale, so the update has to be over before the lookup starts -- DESIGN 7.)
+        self.riders = os.environ.get("N2M_RIDERS", "1") != "0" and world_size == 1 and not opt.sdf and self.ind_dim == 0
         self._tail_ticket = torch.zeros(64 * 32, dtype=torch.int32, device=dev)       # N2M_TAIL_TICKET_WORDS
         self._mid_events = None
         # Live-first sample order for the table backward (round 5; MEASURED AND REJECTED, off by default -- N2M_LIVE_FIRST=1 turns it on).
@@ -1031,6 +1039,7 @@ class Stage0Engine:
             L.call("n2m_sample_order_live_first", _p(b.rays), _p(w["live"]), _p(w["block_live"]), N, M, _p(w["perm"]), s)
             if self._identity_order:
                 torch.arange(M, dtype=torch.int32, device=dev, out=w["perm"][:M])
+        dsum = None
         if M > 0:
             if want_tv and self.tv_at == 2:
                 start_tv()
@@ -1046,9 +1055,18 @@ class Stage0Engine:
                        _p(w["d_h2"]), *[_p(g) for g in self.dw_views], _p(self.dcodes), _p(self._ind_ws), self._ind_ws.numel(), _p(o.found_inf),
                        float(2.0 * opt.lambda_specular / M) if spec_reg else 0.0, _p(seed) if spec_reg else None, s)
             else:
-                L.call("n2m_field_backward_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw], M, shading, 1,
-                       _p(d_sigma), _p(d_rgb), None, _p(w["d_h1"]), _p(w["d_h2"]), *[_p(g) for g in self.dw_views], _p(o.found_inf),
-                       float(2.0 * opt.lambda_specular / M) if spec_reg else 0.0, _p(seed) if spec_reg else None, s)
+                if self.riders and not depth_step and self.fuse_adam is None:
+                    dsum = L.DwSum()      # the backward describes the second stage of its dW reduction here instead of launching it
+                    L.call("n2m_field_backward_defer_dw", ctypes.addressof(dsum))
+                try:
+                    L.call("n2m_field_backward_train", _p(xyzs), _p(dirs) if shading != 0 else None, _p(w["h1"]), _p(w["h2"]), *[_p(p) for p in sw], M, shading, 1,
+                           _p(d_sigma), _p(d_rgb), None, _p(w["d_h1"]), _p(w["d_h2"]), *[_p(g) for g in self.dw_views], _p(o.found_inf),
+                           float(2.0 * opt.lambda_specular / M) if spec_reg else 0.0, _p(seed) if spec_reg else None, s)
+                finally:
+                    if dsum is not None:
+                        L.call("n2m_field_backward_defer_dw", None)
+                if dsum is not None and not dsum.partial:
+                    dsum = None
             L.grid_backward_config(*self._bwd_cfg)
             need = L.lib().n2m_grid_binned_pair_workspace_bytes(M, self.Lv, self.ho.ctypes.data)
             ws = L.workspace(dev, need)
@@ -1129,13 +1147,23 @@ class Stage0Engine:
                                and getattr(self, "_corners_of", None) == (self.global_step, M))      # ... and only if THIS step's forward wrote them
                 if use_corners:      # (sticky thread-local of the library: set in front of the call it is meant for, cleared behind it whatever happens)
                     L.call("n2m_grid_backward_tv_corners", _p(w["tv4"]))
+                carried = ctypes.c_int(0)
+                if dsum is not None:      # (one-shot thread-local of the library, like the event above: the accumulate takes the dW sum along)
+                    L.call("n2m_grid_backward_dw_rider", ctypes.addressof(dsum), ctypes.byref(carried))
                 try:
                     backward(0)
                 finally:
                     if use_corners:
                         L.call("n2m_grid_backward_tv_corners", None)
+                    if dsum is not None:
+                        L.call("n2m_grid_backward_dw_rider", None, None)
+                if carried.value:
+                    dsum = None
                 if mid:
                     self._marker = ev
+            if dsum is not None:
+                # the table backward took a path without the rider kernel (few samples: the tile-major path): the sum as the launch it always was
+                L.call("n2m_field_dw_sum", ctypes.addressof(dsum), s)
         else:
             # no sample in the batch: every gradient is zero (the reduction below still takes part on every rank)
             self.g1.zero_()
