@@ -134,6 +134,23 @@ int n2m_gather_rows_strided(const float* x, const int64_t* idx, uint32_t K, uint
 int n2m_scatter_rows_strided(const float* src, const int64_t* idx, uint32_t K, uint32_t C, uint32_t src_stride, float* dst, uint32_t dst_stride,
                              void* stream);
 
+/* The scene contraction of the unbounded recipes and its inverse (nerf/renderer.py:25-41) on N rows of three floats:
+ *   contract:    mag = max(|x|, |y|, |z|);  mag <= 1 ? x : x * (2 - 1 / mag) / mag
+ *   uncontract:  mag = max(|x|, |y|, |z|);  mag <= 1 ? x : x * (1 / (2 * mag - mag * mag))
+ * in the operation order of the torch statements, every operation rounded on its own: the result equals the statement's on CPU fp32
+ * tensors bit for bit, rows with NaN (-> all NaN, torch.amax hands a NaN on) or infinite components included.  out may be xyz.
+ * N == 0 launches nothing; a NULL tensor with N > 0 is N2M_EINVAL. */
+int n2m_contract(const float* xyz, uint32_t N, float* out, void* stream);
+int n2m_uncontract(const float* xyz, uint32_t N, float* out, void* stream);
+/* The stage-1 executor's surface points in one launch: pts[k, :] = img[idx[k], 0:3] of an image whose rows are `cols_in_stride` (>= 3; 4 for
+ * the RGBA image) floats apart, contracted as above when `contract` is set, and x01[k, :] = pts[k, :] mapped from [-bound, bound] to [0, 1] the
+ * way the grid encoder's caller does it on the device: 0.5 + pts * (0.5 / bound) for a power-of-two bound, else
+ * (pts + bound) * (1 / (2 bound)) (torch's device division by a host scalar multiplies by the reciprocal).  With contract == 0 both outputs
+ * equal n2m_gather_rows_strided followed by those torch statements bit for bit.  img is only read.  K == 0 launches nothing; a NULL tensor
+ * with K > 0, a stride below 3 or a bound that is not positive and finite is N2M_EINVAL. */
+int n2m_gather_contract_x01(const float* img, const int64_t* idx, uint32_t K, uint32_t cols_in_stride, int contract, float bound, float* pts,
+                            float* x01, void* stream);
+
 /* Stage-1 image head, forward AND backward in one launch: what nerf/renderer.py:886-913 does with the two antialias outputs (clamp,
  * image = alpha * rgb, depth = alpha * z/w, T = 1 - alpha, ssaa reduction by `scale_img_hwc` = bilinear minification (exactly the 2 x 2
  * mean for ssaa 2) and nearest for the triangle id, image + T * bg, weights_sum = 1 - T) plus the per-pixel loss of nerf/utils.py:708-721

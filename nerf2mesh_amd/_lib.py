@@ -184,6 +184,9 @@ SIGNATURES = {
     "n2m_gather_rows_strided": [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp],
     "n2m_scatter_rows_strided": [_vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp],
     "n2m_scatter_rows": [_vp, _vp, _u32, _u32, _vp, _vp],
+    "n2m_contract": [_vp, _u32, _vp, _vp],
+    "n2m_uncontract": [_vp, _u32, _vp, _vp],
+    "n2m_gather_contract_x01": [_vp, _vp, _u32, _u32, _int, _f32, _vp, _vp, _vp],
     "n2m_stage1_head": [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp],
     # include/n2m_peer.h
     "n2m_peer_alloc": [ctypes.c_size_t, _int, ctypes.POINTER(_vp)],

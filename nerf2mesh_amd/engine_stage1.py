@@ -2,7 +2,8 @@
 as a FIXED SEQUENCE OF C-ABI CALLS on preallocated buffers -- no autograd graph, no per-step allocation, the backward written out by hand:
 
   verts = vertices + offsets -> n2m_to_clip -> n2m_rasterize_forward -> n2m_interpolate_forward x2 (positions, coverage)
-  -> covered-pixel list (the ONE host read of the step: the shading kernels are sized by it) -> n2m_gather_rows x2
+  -> covered-pixel list (the ONE host read of the step: the shading kernels are sized by it) -> n2m_gather_contract_x01 (surface points,
+     contracted under opt.contract, and their table coordinates) + n2m_gather_rows (directions)
   -> n2m_grid_encode_forward (colour table, fp16) -> n2m_field_forward (colour + specular networks) -> n2m_scatter_rows (RGB + alpha image)
   -> n2m_antialias_forward -> n2m_stage1_head (clamp, alpha * rgb, ssaa reduction, background blend, loss, face errors AND the gradient
      w.r.t. the antialias output, loss scale applied)
@@ -35,7 +36,7 @@ class Stage1Engine:
     @staticmethod
     def supported(tr):
         opt, model = tr.opt, tr.model
-        return (tr.amp_adam and tr.fused_head and tr.packed_aa and bool(getattr(opt, "fused_mlp", False)) and not opt.contract
+        return (tr.amp_adam and tr.fused_head and tr.packed_aa and bool(getattr(opt, "fused_mlp", False))
                 and not opt.enable_offset_nerf_grad and getattr(model, "individual_dim", 0) == 0 and opt.lambda_lap > 0 and opt.lambda_offsets > 0
                 and model.vertices.is_cuda and int(opt.ssaa) in (1, 2))
 
@@ -71,7 +72,6 @@ class Stage1Engine:
         self.partials = f(nb_head + nb_reg + nb_mesh)      # [image head's | regularisers' | mesh losses'] workgroup sums: ONE reduction gives the step's loss
         self.partial, self.reg_partial = self.partials[:nb_head], self.partials[nb_head:nb_head + nb_reg]
         self.mesh_partial = self.partials[nb_head + nb_reg:] if nb_mesh else None
-        self.half = torch.tensor(0.5, dtype=torch.float32, device=dev)
         self.zero = torch.zeros((), dtype=torch.float32, device=dev)
         self.cap = 0
         # covered pixels of the frame (nerf/renderer.py:862-863 `mask_flatten`): the library's own order-preserving selection (n2m_select_positive: three
@@ -98,7 +98,7 @@ class Stage1Engine:
             o += p.numel()
         self.table = dr._topology(model.triangles)
         self.bound = float(model.bound)
-        self.pow2_bound = float(np.log2(self.bound)).is_integer()
+        self.contract = int(bool(opt.contract))
         # the optimizer reads the executor's buffers
         opt_ = tr.optimizer
         opt_.half_grads[enc.embeddings] = lambda: self.g2
@@ -174,14 +174,12 @@ class Stage1Engine:
             if K > 0:
                 self._grow(K)
                 pts, dsel, x01, rgb = self.pts[:K], self.dsel[:K], self.x01[:K], self.rgb[:K]
-                L.call("n2m_gather_rows_strided", _p(self.rgba), _p(idx), K, 3, 4, _p(pts), 3, s)
+                # surface points of the covered pixels, contracted under opt.contract (nerf/renderer.py:872-873: the colour field reads the
+                # contracted point, and so does its table), and their table coordinates (x + bound) / (2 bound) (grid.py:156), in one launch.
+                # The points are detached (no enable_offset_nerf_grad here): no gradient passes the contraction.
+                L.call("n2m_gather_contract_x01", _p(self.rgba), _p(idx), K, 4, self.contract, self.bound, _p(pts), _p(x01), s)
                 L.call("n2m_gather_rows", _p(dirs), _p(idx), K, 3, _p(dsel), s)
                 # ---- colour field of the covered pixels (nerf/renderer.py:875-881, nerf/network.py:159-189 under autocast)
-                if self.pow2_bound:
-                    torch.add(self.half, pts, alpha=0.5 / self.bound, out=x01)               # == (x + bound) / (2 bound) bit for bit (grid.py:156)
-                else:
-                    torch.add(pts, self.bound, out=x01)
-                    x01.div_(2.0 * self.bound)
                 emb2h = self.enc.half_table()
                 L.call("n2m_grid_encode_forward", _p(x01), _p(emb2h), _p(self.enc.offsets), _p(self.h2), K, 3, 2, self.levels, self.levels, self.geo[0],
                        self.geo[1], None, self.geo[2], self.geo[3], self.geo[4], L.F16, s)

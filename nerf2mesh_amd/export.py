@@ -166,6 +166,25 @@ def read_mlp_json(path):
 # The two pymeshlab selections export_stage0 uses between marching cubes and the PLY (meshutils.py:63-143), on device tensors.
 # (clean_mesh and decimate_mesh, meshutils.py:27-60,146-190, run on the device too: mesh_clean.clean_mesh, mesh_simplify.decimate.)
 
+def load_stage0_meshes(path, cascade):
+    """The stage-0 meshes stage 1 starts from (nerf/renderer.py:130-153): <path>/mesh_{cas}.ply for cas = 0 .. cascade - 1, concatenated,
+    the faces of cascade `cas` shifted by the vertices in front of it.  Returns (vertices [V,3] float32, triangles [F,3] int32, v_cumsum,
+    f_cumsum), the two lists with one entry more than there are cascades.  A missing mesh_0.ply raises, as the reference does; the list
+    ends in front of the first later cascade whose file is missing: export_stage0 writes no file for a cascade (the SDF recipe's outer
+    shell among them) that its removals emptied, and stage 1 then runs on the cascades in front of it -- one cascade, for an emptied shell."""
+    vs, fs, v_cumsum, f_cumsum = [], [], [0], [0]
+    for cas in range(int(cascade)):
+        file = os.path.join(path, f"mesh_{cas}.ply")
+        if cas > 0 and not os.path.exists(file):
+            break
+        v, f = read_ply(file)
+        vs.append(np.asarray(v, dtype=np.float32))
+        fs.append(np.asarray(f, dtype=np.int32) + np.int32(v_cumsum[-1]))
+        v_cumsum.append(v_cumsum[-1] + int(v.shape[0]))
+        f_cumsum.append(f_cumsum[-1] + int(f.shape[0]))
+    return np.concatenate(vs, axis=0), np.concatenate(fs, axis=0), v_cumsum, f_cumsum
+
+
 def remove_vertices(vertices, triangles, selected):
     """Deletes the selected vertices and every face that touches one (`meshing_remove_selected_vertices`, meshutils.py:122-143);
     the remaining vertices keep their order.  vertices [V,3], triangles [F,3] int, selected [V] bool -> (vertices', triangles')."""

@@ -70,9 +70,33 @@ def percentile_linear(x, q):
     return torch.where(g >= 0.5, b - d * (1 - g), a + d * g)
 
 
+def _contract_rows(name, xyzs):
+    """n2m_contract / n2m_uncontract on a device tensor [N,3] fp32 with no graph attached: one launch, the bits of the torch statement."""
+    from . import _lib as L
+    x = xyzs.contiguous()
+    out = torch.empty_like(x)
+    L.call(name, L.ptr(x), x.shape[0], L.ptr(out), L.stream())
+    return out
+
+
+def _device_rows(xyzs):
+    return xyzs.is_cuda and xyzs.dim() == 2 and xyzs.shape[1] == 3 and xyzs.dtype == torch.float32 and not (torch.is_grad_enabled() and xyzs.requires_grad)
+
+
 def contract(xyzs):
+    """nerf/renderer.py:25-32.  Device rows without a gradient take one launch (n2m_contract, same bits); everything else the statement."""
+    if _device_rows(xyzs):
+        return _contract_rows("n2m_contract", xyzs)
     mag = torch.amax(torch.abs(xyzs), dim=1, keepdim=True)
     return torch.where(mag <= 1, xyzs, xyzs * (2 - 1 / mag) / mag)
+
+
+def uncontract(xyzs):
+    """The inverse (nerf/renderer.py:34-41): points of the contracted cube (-2, 2)^3 back to world space.  Device route as `contract`."""
+    if _device_rows(xyzs):
+        return _contract_rows("n2m_uncontract", xyzs)
+    mag = torch.amax(torch.abs(xyzs), dim=1, keepdim=True)
+    return torch.where(mag <= 1, xyzs, xyzs * (1 / (2 * mag - mag * mag)))
 
 
 def dilate_cross(a):
@@ -538,8 +562,16 @@ class NeRFRenderer(nn.Module):
         (:653-655); min_f / min_d are opt.clean_min_f / clean_min_d.  decimate=True honours `decimate_target` where the reference does,
         with the device decimation of mesh_simplify.py: the inner mesh after its visibility filter (and cleaning) to `decimate_target` faces
         with optimal placement (:540-541), the outer cascades to `decimate_target // 2` without it, before their visibility filter
-        (:582-583, :658-659).  With neither (the default) the raw iso-surfaces are written.  NOT done: the SDF recipe's contracted outer
-        shell (:548-601).  dataset: object with `.mvps [B,4,4]`, `.H`, `.W` for the visibility test, or None.
+        (:582-583, :658-659).  With neither (the default) the raw iso-surfaces are written.
+        SDF recipe with bound > 1 (the contracted background, :548-601): the outer shell mesh_1.ply.  The field is queried at
+        2 * linspace(-1, 1, R)^3 (contracted coordinates, R = resolution), nan_to_num, marching cubes of -sdf at 0; the vertices with all
+        |x| <= 0.5 (the unit box, which mesh_0 covers) go, the rest is scaled by 2 - 2 / R, cleaned (clean=True, repair=False), decimated to
+        2 * decimate_target faces without optimal placement (decimate=True, when it has more), brought back to world space by
+        `uncontract`, cut at aabb_train (any coordinate <= lo or >= hi goes) and visibility-filtered (dataset).  The lattice is queried
+        whatever resolution == grid_size is: the reference reuses the X, Y, Z of its lattice branch there and raises a NameError when
+        that branch did not run.  A shell that any removal empties is skipped -- no file, no key, like an emptied density-mode cascade --
+        and stage 1 then has ONE cascade: its loader (export.load_stage0_meshes) stops at the first missing mesh_{cas}.ply.
+        dataset: object with `.mvps [B,4,4]`, `.H`, `.W` for the visibility test, or None.
         Returns {cascade: (vertices [V,3] f32, triangles [F,3] i32)} (device tensors)."""
         import os
         from . import export
@@ -603,7 +635,45 @@ class NeRFRenderer(nn.Module):
                     v, t = export.remove_faces(v, t, unseen, dilation=getattr(self.opt, "visibility_mask_dilation", 5))
                 meshes[cas] = (v, t)
                 export.write_ply(os.path.join(save_path, f"mesh_{cas}.ply"), v.cpu().numpy(), t.cpu().numpy())
+        elif self.bound > 1:
+            shell = self._sdf_outer_shell(resolution, S, dec_target, dataset, clean)
+            if shell is not None:
+                meshes[1] = shell
+                export.write_ply(os.path.join(save_path, "mesh_1.ply"), shell[0].cpu().numpy(), shell[1].cpu().numpy())
         return meshes
+
+    def _sdf_outer_shell(self, resolution, S, dec_target, dataset, clean):
+        """The contracted background of the SDF recipe as a world-space mesh (nerf/renderer.py:548-601, in its order), or None when a
+        removal leaves nothing.  dec_target: the inner mesh's face target (0: no decimation); the shell's is twice that (:581)."""
+        from . import export
+        from .marching_cubes import marching_cubes
+        from .mesh_clean import clean_mesh
+        from .mesh_simplify import decimate as decimate_mesh
+        sigmas = torch.nan_to_num(self.density_volume(resolution, S, scale=2.0), 0)
+        v, t = marching_cubes(-sigmas, 0.0, div=resolution - 1.0, mul=2.0, add=-1.0)
+        r = 0.5
+        v, t = export.remove_vertices(v, t, (v.abs() <= r).all(dim=1))
+        if v.shape[0] == 0:
+            return None
+        bound = 2
+        v = v * (bound - bound / resolution)
+        if clean:
+            v, t, _ = clean_mesh(v, t, min_f=self.opt.clean_min_f, min_d=self.opt.clean_min_d, repair=False)
+            if v.shape[0] == 0:
+                return None
+        if dec_target and t.shape[0] > 2 * dec_target:
+            v, t, _ = decimate_mesh(v, t, 2 * dec_target, optimal_placement=False)
+        v = uncontract(v.float().contiguous())
+        lo, hi = self.aabb_train[:3], self.aabb_train[3:]
+        v, t = export.remove_vertices(v, t, ((v <= lo) | (v >= hi)).any(dim=1))
+        if v.shape[0] == 0:
+            return None
+        if dataset is not None and t.shape[0] > 0:
+            unseen = self.mark_unseen_triangles(v, t, dataset.mvps, dataset.H, dataset.W)
+            v, t = export.remove_faces(v, t, unseen, dilation=getattr(self.opt, "visibility_mask_dilation", 5))
+            if v.shape[0] == 0:
+                return None
+        return v, t
 
     # ------------------------------------------------------------------------------------------ stage 1
     @torch.no_grad()

@@ -630,7 +630,9 @@ class Stage1Trainer:
     + Laplacian smoothness, + offset L2), Adam on colour networks + vertex offsets."""
 
     def __init__(self, model, opt, poses, vertices, triangles, device, H=synthetic.LEGO_HW, W=synthetic.LEGO_HW, rank=0, world_size=1, seed=0,
-                 capture=None):
+                 capture=None, v_cumsum=None, f_cumsum=None):
+        """vertices / triangles: the stage-0 mesh, every cascade concatenated (export.load_stage0_meshes); v_cumsum / f_cumsum: where each
+        cascade begins and ends in them (None: one cascade)."""
         self.model, self.opt, self.device = model.to(device), opt, device
         # capture (capture.Capture, opt-in): views, size, intrinsics and model-view-projections of a captured image set; the view cache is then
         # filled by n2m_capture_view (rays, decoded ground truth, unit directions) instead of rays_from_pixels + render_gt
@@ -642,7 +644,7 @@ class Stage1Trainer:
         self.poses = poses.to(device)
         self.views = list(range(rank, poses.shape[0], world_size))            # views shard across ranks
         self.mvps = capture.mvps if capture is not None else torch.stack([synthetic.mvp_matrix(p, H, W) for p in self.poses])
-        model.init_stage1(vertices, triangles)
+        model.init_stage1(vertices, triangles, v_cumsum, f_cumsum)
         params = model.get_params(opt.lr) + [{"params": model.vertices_offsets, "lr": opt.lr_vert, "weight_decay": 0}]
         # main.py:221 Adam(eps=1e-15) + nerf/utils.py:506 GradScaler, as in stage 0: optim.FusedAdamAMP does both in two launches (torch:
         # unscale + inf check + four multi-tensor Adam launches, 0.35 ms of host time per step of a step that is host-bound) and refreshes

@@ -25,6 +25,8 @@ ap.add_argument("--iters0", type=int, default=3000)
 ap.add_argument("--iters1", type=int, default=300)
 ap.add_argument("--resolution", type=int, default=256)
 ap.add_argument("--texture", type=int, default=1024)
+ap.add_argument("--sdf", action="store_true", help="the SDF recipe; with --bound 2 the contracted one, whose outer shell becomes mesh_1.ply")
+ap.add_argument("--bound", type=float, default=1)
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -35,9 +37,14 @@ def clock(label, t0, extra=""):
     print(f"[{label}] {time.perf_counter() - t0:7.3f} s  {extra}", flush=True)
 
 
-opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=True)
+opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 1 / 256, iters=args.iters0, fused_mlp=True, sdf=args.sdf)
 poses = S.make_cameras(100, seed=0)
-eng = Stage0Engine(NeRFNetwork(opt), opt, poses, dev, seed=0)
+net = NeRFNetwork(opt)
+if Stage0Engine.supported(net, opt):
+    eng = Stage0Engine(net, opt, poses, dev, seed=0)
+else:
+    from nerf2mesh_amd.trainer import Stage0Trainer
+    eng = Stage0Trainer(net, opt, poses, dev, seed=0)
 eng.mark_untrained()
 eng.train_step()
 torch.cuda.synchronize()
@@ -52,10 +59,12 @@ meshes = model.export_stage0(os.path.join(args.out, "mesh_stage0"), resolution=a
 v, t = meshes[0]
 clock("export_stage0", t0, f"{args.resolution}^3 density volume -> {v.shape[0]} vertices, {t.shape[0]} triangles (raw iso-surface)")
 
-rv, rt = export.read_ply(os.path.join(args.out, "mesh_stage0", "mesh_0.ply"))
 opt1 = opt
 opt1.stage, opt1.iters = 1, max(args.iters1, 501)
-tr = Stage1Trainer(model, opt1, poses, torch.from_numpy(rv), torch.from_numpy(rt), dev)
+# every cascade export_stage0 wrote: mesh_0.ply, and under --sdf --bound 2 the outer shell mesh_1.ply
+n_cas = model.cascade if opt.sdf else 1
+rv, rt, v_cumsum, f_cumsum = export.load_stage0_meshes(os.path.join(args.out, "mesh_stage0"), n_cas)
+tr = Stage1Trainer(model, opt1, poses, torch.from_numpy(rv), torch.from_numpy(rt), dev, v_cumsum=v_cumsum, f_cumsum=f_cumsum)
 tr.train_step()
 torch.cuda.synchronize()
 t0 = time.perf_counter()

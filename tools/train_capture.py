@@ -22,7 +22,10 @@
      `train_loss_tail` is the mean stage-0 training loss over the last 100 steps and `ind_dim` the code width (--ind_dim): two runs of the same
      schedule and seed with --ind_dim 0 and 8 report what the per-image codes buy on a set whose exposure varies.
 
-Reads nothing but PATH; writes under --workspace.  With --bound > 1 stage 1 refines the inner mesh (cascade 0) only."""
+Reads nothing but PATH; writes under --workspace.  With --bound > 1 stage 1 refines the inner mesh (cascade 0) only, except under --sdf:
+`--sdf --bound 2` is the SDF recipe on an unbounded scene (contracted background), export_stage0 then writes the outer shell as mesh_1.ply
+and stage 1 loads both files (export.load_stage0_meshes; one cascade when the shell came out empty).  That recipe switches the offset
+gradient on, which the stage-1 executor does not cover: its stage 1 runs on the autograd trainer."""
 import argparse
 import json
 import os
@@ -57,6 +60,7 @@ ap.add_argument("--enable_cam_center", action="store_true")
 ap.add_argument("--lambda_depth", type=float, default=0.1)
 ap.add_argument("--offset", type=float, nargs=3, default=[0, 0, 0])
 ap.add_argument("--bound", type=float, default=1)
+ap.add_argument("--sdf", action="store_true", help="the SDF recipe (main.py:138-153); with --bound > 1 the scene is contracted and the outer shell exported")
 ap.add_argument("--color_space", choices=["srgb", "linear"], default="srgb")
 ap.add_argument("--resolution", type=int, default=None, help="marching-cubes resolution (default: the occupancy grid's)")
 ap.add_argument("--decimate_target", type=float, default=3e5)
@@ -116,7 +120,7 @@ opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 
                    offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace,
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
                    enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics,
-                   lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num)
+                   lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf)
 model = NeRFNetwork(opt)
 if colmap:
     model.to(dev)
@@ -145,7 +149,14 @@ if f0.shape[0] == 0:
 
 # ---- stage 1
 opt.stage, opt.iters = 1, max(args.iters1, 501)
-tr = Stage1Trainer(model, opt, None, v0, f0, dev, seed=args.seed, capture=cap)
+if opt.sdf and model.cascade > 1:          # the contracted recipe: every cascade export_stage0 wrote (mesh_0.ply, and mesh_1.ply unless the shell was empty)
+    from nerf2mesh_amd import export
+    va, fa, v_cumsum, f_cumsum = export.load_stage0_meshes(os.path.join(args.workspace, "mesh_stage0"), model.cascade)
+    print(f"[stage 1] {len(v_cumsum) - 1} cascade(s): vertices {v_cumsum}, faces {f_cumsum}", flush=True)
+    tr = Stage1Trainer(model, opt, None, torch.from_numpy(va), torch.from_numpy(fa), dev, seed=args.seed, capture=cap, v_cumsum=v_cumsum,
+                       f_cumsum=f_cumsum)
+else:
+    tr = Stage1Trainer(model, opt, None, v0, f0, dev, seed=args.seed, capture=cap)
 step = Stage1Engine(tr).train_step if Stage1Engine.supported(tr) else tr.train_step
 t0 = time.perf_counter()
 for _ in range(args.iters1):
