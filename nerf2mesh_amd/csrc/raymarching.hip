@@ -1005,9 +1005,14 @@ composite_train_bwd_kernel(const float* __restrict__ grad_weights, const float* 
         if (live) {
             grad_rgbs[3 * i] = gi0 * w; grad_rgbs[3 * i + 1] = gi1 * w; grad_rgbs[3 * i + 2] = gi2 * w;
             const float scale = alpha_mode ? (1.0f / (1.0f - alpha)) : dt;
-            grad_sigmas[i] = scale * (gi0 * (T_after * cr - (rF - r)) + gi1 * (T_after * cg - (gF - g)) +
-                                      gi2 * (T_after * cb - (bF - b)) + (gws + gw) * (T_after - (wsF - ws)) +
-                                      gd * (T_after * tmid - (dF - d)));
+            // alpha mode: the ray's last live sample has nothing behind it, so its suffix sums are exact zeros -- not the residue of two
+            // differently ordered sums (the forward's totals, this scan), ~eps * total, which 1 / (1 - alpha) multiplies by up to 1e4 on the
+            // opaque sample a stop falls on.  Density mode keeps its expression (the factor there is dt) and its bits.
+            const bool tail = alpha_mode && (stop ? lane == last : k + 1 == cnt);
+            const float sr = tail ? 0.f : rF - r, sg_ = tail ? 0.f : gF - g, sb = tail ? 0.f : bF - b, sw = tail ? 0.f : wsF - ws, sd = tail ? 0.f : dF - d;
+            grad_sigmas[i] = scale * (gi0 * (T_after * cr - sr) + gi1 * (T_after * cg - sg_) +
+                                      gi2 * (T_after * cb - sb) + (gws + gw) * (T_after - sw) +
+                                      gd * (T_after * tmid - sd));
         } else if (valid) {
             grad_sigmas[i] = 0.f; grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f;
         }
@@ -1202,8 +1207,12 @@ composite_loss_train_kernel(const float* __restrict__ sigmas, const float* __res
                     // DEPTH: its grad_depth term, and the same + 0 as before for a ray without one (gd == 0), so those rays keep their bits
                     const float gw = ENT ? gE * n2m_entropy_grad(w) : 0.f;      // grad_weights[i]
                     const float gscl = ALPHA ? 1.0f / (1.0f - alpha) : dt;      // (alpha = 1: inf, un-guarded like the reference; the caller clips alpha)
-                    grad_sigmas[i] = gscl * (gi[0] * (T_after * cr - (rF - r)) + gi[1] * (T_after * cg - (gF - g)) +
-                                           gi[2] * (T_after * cb - (bF - b)) + (gws + gw) * (T_after - (wsF - ws)) +
+                    // ALPHA: the last live sample's suffix sums are exact zeros, as in composite_train_bwd_kernel (the other instantiations
+                    // compile to the expression they had)
+                    const bool tail = ALPHA && (stop ? lane == last : k + 1 == cnt);
+                    const float sr = tail ? 0.f : rF - r, sg = tail ? 0.f : gF - g, sb = tail ? 0.f : bF - b, sw = tail ? 0.f : wsF - ws;
+                    grad_sigmas[i] = gscl * (gi[0] * (T_after * cr - sr) + gi[1] * (T_after * cg - sg) +
+                                           gi[2] * (T_after * cb - sb) + (gws + gw) * (T_after - sw) +
                                            ((DEPTH && gd != 0.f) ? gd * (T_after * tmid - (dF - d)) : 0.f * 0.f));
                 } else if (valid) {
                     grad_sigmas[i] = 0.f; grad_rgbs[3 * i] = 0.f; grad_rgbs[3 * i + 1] = 0.f; grad_rgbs[3 * i + 2] = 0.f;
