@@ -992,6 +992,26 @@ int n2m_sh_encode_backward(const float* grad, const float* inputs, uint32_t B, u
                            const float* dy_dx, float* grad_inputs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * image metrics (csrc/metrics.hip; not a reference extension: the reference's trainer carries an SSIM meter, commented out, that
+ * calls torchmetrics -- nerf/utils.py:351-465)
+ * ---------------------------------------------------------------------------------------------------- */
+
+/* SSIM (Wang et al. 2004) of x (prediction) against y (target), fp32 [H, W, C] channel-last, contiguous; C 1 or 3, H, W >= 11 (else
+ * N2M_EINVAL).  Window: 11 x 11 Gaussian, separable; taps_host: its 11 taps, a HOST array (float64 exp, normalised to sum 1, rounded to
+ * fp32 by the caller).  VALID windows only: the map is [H - 10, W - 10, C]; C1 = 0.01^2, C2 = 0.03^2.
+ * map_or_null: the per-window S; dS_or_null: [3, H - 10, W - 10, C] = dS/dmu_x, dS/dE[x^2], dS/dE[xy] per window (what
+ * n2m_ssim_backward reads); partials: n2m_ssim_partials(H, W) floats of scratch (one sum per workgroup); out[0] = mean of S, summed in a
+ * fixed order (no float atomics: two calls give the same bits). */
+uint32_t n2m_ssim_partials(uint32_t H, uint32_t W);
+int n2m_ssim_forward(const float* x, const float* y, uint32_t H, uint32_t W, uint32_t C, const float* taps_host, float* map_or_null,
+                     float* dS_or_null, float* partials, float* out, void* stream);
+/* grad_x[p] = g[0] / n_windows_total * sum over windows q containing p of w(p - q) (A[q] + 2 x[p] B[q] + y[p] Cq[q]), (A, B, Cq) = the three
+ * planes of dS; n_windows_total = (H - 10)(W - 10) C.  g: the DEVICE scalar gradient of the mean.  Overwrites grad_x [H, W, C]; no gradient
+ * with respect to y. */
+int n2m_ssim_backward(const float* x, const float* y, const float* dS, uint32_t H, uint32_t W, uint32_t C, const float* taps_host,
+                      const float* g, float* grad_x, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * per-kernel timing (measurement support for bench.py; not part of the reference surface)
  * ---------------------------------------------------------------------------------------------------- */
 

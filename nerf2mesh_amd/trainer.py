@@ -690,6 +690,14 @@ class Stage1Trainer:
         self._dirs = {}               # per view: unit directions at the ssaa resolution (30 MB per 800 x 800 view at ssaa 2)
         self.covered_seen = 0         # shaded (covered) full-resolution pixels so far: the unit of the stage-1 byte model
         self.fused_head = torch.device(device).type == "cuda" and int(opt.ssaa) in (1, 2)      # losses.stage1_head (False: the torch graph)
+        # lambda_ssim > 0 (not a reference option): adds lambda_ssim * (1 - SSIM) of the whole frame (metrics.ssim) -- the structural term the
+        # reference takes from LPIPS on patches (--lambda_lpips).  It needs the image itself, so it selects the torch-graph head; the fused
+        # head and the executor (Stage1Engine.supported requires fused_head) do not carry it.
+        self.lambda_ssim = float(getattr(opt, "lambda_ssim", 0) or 0)
+        if self.lambda_ssim > 0:
+            if H < 11 or W < 11:
+                raise ValueError(f"lambda_ssim > 0 needs frames of at least 11 x 11 pixels (one valid SSIM window), got {H} x {W}")
+            self.fused_head = False
         self.packed_aa = os.environ.get("N2M_S1_PACKED_AA", "1") != "0"      # one antialias call on RGB + alpha instead of two
 
     _lambda_mask = Stage0Trainer._lambda_mask
@@ -808,6 +816,9 @@ class Stage1Trainer:
             if opt.refine:
                 model.update_triangles_errors(loss.detach())
             loss = loss.mean()
+            if self.lambda_ssim > 0:
+                from .metrics import ssim
+                loss = loss + self.lambda_ssim * (1 - ssim(out["image"].view(self.H, self.W, 3), gt_rgb.view(self.H, self.W, 3)))
         self.covered_seen += getattr(model, "last_covered", 0)
         if verts is not None and verts.is_cuda and opt.lambda_lap > 0 and opt.lambda_offsets > 0:
             # both mesh regularisers (nerf/utils.py:761-789) as one value, one launch each way

@@ -1,0 +1,98 @@
+#!/usr/bin/env python3
+"""Held-out PSNR and SSIM of every stage's product on the same views: the field (stage-0 inference render), the stage-1 mesh
+(render_stage1) and the exported asset loaded back from its files (asset.ExportedAsset.render), each against the ground truth on white.
+
+    tools/evaluate.py [--iters0 N --iters1 N --views N --size S --lambda_ssim w]            the short synthetic pipeline (tools/eval_export.py's flow)
+    tools/evaluate.py --data PATH [--data_format nerf|colmap|dtu] [--split test|val|...]   a captured set: trains on its train split, evaluates --split
+
+Prints one table row per view and stage, then one JSON line.  LPIPS, the reference's other meter, is not built (no VGG weights here)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+from nerf2mesh_amd import export, metrics, synthetic as S
+from nerf2mesh_amd.asset import ExportedAsset
+from nerf2mesh_amd.capture import Capture
+from nerf2mesh_amd.engine import Stage0Engine
+from nerf2mesh_amd.engine_stage1 import Stage1Engine
+from nerf2mesh_amd.network import NeRFNetwork
+from nerf2mesh_amd.options import make_options
+from nerf2mesh_amd.trainer import Stage0Trainer, Stage1Trainer
+
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--out", default="bench_runs/evaluate")
+ap.add_argument("--data", default=None, help="a captured set (default: the synthetic box scene)")
+ap.add_argument("--data_format", choices=["nerf", "colmap", "dtu"], default="nerf")
+ap.add_argument("--split", default=None, help="held-out split of --data (default: test for nerf, val for colmap / dtu)")
+ap.add_argument("--downscale", type=int, default=1)
+ap.add_argument("--iters0", type=int, default=3000)
+ap.add_argument("--iters1", type=int, default=300)
+ap.add_argument("--resolution", type=int, default=256)
+ap.add_argument("--texture", type=int, default=2048)
+ap.add_argument("--views", type=int, default=8, help="held-out views")
+ap.add_argument("--size", type=int, default=400, help="synthetic: side of the held-out frames")
+ap.add_argument("--lambda_ssim", type=float, default=0.0, help="stage 1: weight of 1 - SSIM (0: the reference's loss)")
+args = ap.parse_args()
+dev = torch.device("cuda", 0)
+torch.manual_seed(0)
+
+opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=True, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
+                   per_view_intrinsics=args.data_format == "dtu")
+model = NeRFNetwork(opt)
+if args.data is None:
+    cap, poses = None, S.make_cameras(100, seed=0)
+    f = S.LEGO_FOCAL * args.size / S.LEGO_HW
+    held = Capture.synthetic(S.make_cameras(args.views, seed=1), H=args.size, W=args.size, intrinsics=(f, f, args.size / 2, args.size / 2), device=dev)
+    views = list(range(len(held)))
+else:
+    def load(split):
+        if args.data_format == "dtu":
+            return Capture.load_dtu(args.data, split=split, downscale=args.downscale, device=dev)
+        if args.data_format == "colmap":
+            c = Capture.load_colmap(args.data, split=split, downscale=args.downscale, device=dev)
+            c.cam_near_far = None
+            return c
+        return Capture.load_nerf(args.data, split=split, downscale=args.downscale, device=dev)
+    cap, poses = load("train"), None
+    held = load(args.split or ("test" if args.data_format == "nerf" else "val"))
+    views = list(range(0, len(held), max(1, len(held) // max(1, args.views))))[:args.views]
+    if args.data_format == "colmap":
+        model.to(dev)
+        model.update_aabb(cap.pts_aabb.to(dev))
+
+# ---- stage 0 -> mesh -> stage 1 -> files
+cls = Stage0Engine if cap is None or Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
+eng = cls(model, opt, poses, dev, seed=0, capture=cap)
+eng.mark_untrained()
+for _ in range(args.iters0):
+    eng.train_step()
+model.eval()
+with eng.averaged_parameters():
+    field = metrics.evaluate_views(metrics.field_renderer(model, held), held, views)
+    model.export_stage0(os.path.join(args.out, "mesh_stage0"), resolution=args.resolution, **({} if cap is None else dict(dataset=cap, clean=True, decimate=True)))
+rv, rt = export.read_ply(os.path.join(args.out, "mesh_stage0", "mesh_0.ply"))
+opt.stage, opt.iters = 1, max(args.iters1, 501)
+tr = Stage1Trainer(model, opt, poses, torch.from_numpy(rv), torch.from_numpy(rt), dev, capture=cap)
+step = Stage1Engine(tr).train_step if Stage1Engine.supported(tr) else tr.train_step
+for _ in range(args.iters1):
+    step()
+torch.cuda.synchronize()
+model.eval()
+print(f"[pipeline] stage 0: {args.iters0} steps ({cls.__name__}); stage 1: {args.iters1} steps on {rt.shape[0]} faces, lambda_ssim {args.lambda_ssim:g} "
+      f"({'executor' if Stage1Engine.supported(tr) else 'autograd trainer'}); {len(views)} held-out views {held.H} x {held.W}", flush=True)
+mesh = metrics.evaluate_views(metrics.mesh_renderer(model, held), held, views)
+out_dir = os.path.join(args.out, "mesh_stage1")
+model.export_stage1(out_dir, args.texture, args.texture, atlas="charts")
+asset = metrics.evaluate_views(metrics.asset_renderer(ExportedAsset.load(out_dir), held, ssaa=int(opt.ssaa)), held, views)
+
+stages = (("field", field), ("mesh", mesh), ("asset", asset))
+print(f"{'view':>5s} " + " ".join(f"{n + ' PSNR':>11s} {n + ' SSIM':>11s}" for n, _ in stages))
+for k, v in enumerate(views):
+    print(f"{v:5d} " + " ".join(f"{ev['psnr'][k]:11.2f} {ev['ssim'][k]:11.4f}" for _, ev in stages))
+print(f"{'mean':>5s} " + " ".join(f"{ev['mean_psnr']:11.2f} {ev['mean_ssim']:11.4f}" for _, ev in stages), flush=True)
+print(json.dumps({"views": views, "H": held.H, "W": held.W, "iters0": args.iters0, "iters1": args.iters1, "lambda_ssim": args.lambda_ssim,
+                  "faces": int(rt.shape[0]), **{n: {k: ev[k] for k in ("psnr", "ssim", "mean_psnr", "mean_ssim")} for n, ev in stages}}))
