@@ -826,6 +826,28 @@ int n2m_capture_view(const float* poses, uint32_t V, uint32_t view, uint32_t H, 
                      void* stream);
 /* k x k integer box mean of every channel, (sum + k*k/2) / (k*k); src [V,H,W] words -> dst [V,H/k,W/k]; partial blocks are dropped. */
 int n2m_capture_box_downscale(const uint32_t* src, uint32_t V, uint32_t H, uint32_t W, uint32_t k, uint32_t* dst, void* stream);
+/* Lens undistortion of a whole bank, out of place (capture.Capture.load_colmap(undistort=True), what COLMAP's image_undistorter does): the
+ * set becomes pinhole once, at load.  Output pixel (row, col) of view v:
+ *   x = (col + 0.5 - cx_o) / fx_o, y = (row + 0.5 - cy_o) / fy_o           the OUTPUT camera out_intrinsics (pixel centres as n2m_get_rays; y down)
+ *   (xd, yd) = lens(x, y)                                                  COLMAP's forward model (https://colmap.github.io/cameras.html), row `lens`:
+ *        N2M_LENS_BROWN    (k1, k2, p1, p2, 0, 0, 0, 0)   SIMPLE_RADIAL, RADIAL, OPENCV; all zero: a pinhole
+ *        N2M_LENS_FISHEYE  (k1, k2, k3, k4, 0, 0, 0, 0)   OPENCV_FISHEYE (the polynomial in theta = atan r)
+ *   u = fx_s xd + cx_s, v = fy_s yd + cy_s                                 the SOURCE camera src_intrinsics
+ *   depth == 0   src / dst [V,H,W] packed RGBA8 words (R in the low byte): four-tap bilinear at (u - 0.5, v - 0.5) of each of the four
+ *                8-bit channels, taps clamped to the image, rounded to nearest (floor(val + 0.5)) and clamped to [0, 255]
+ *   depth != 0   src / dst [V,H,W] f32: the value of the source texel that contains (u, v), (floor(v), floor(u)) clamped -- a depth map
+ *                is never averaged across a silhouette; every output value is one of the source plane's
+ * src_intrinsics / out_intrinsics: rows (fx, fy, cx, cy) f32, lens: rows of 8 f32; all three device pointers, 16-byte aligned.  per_view != 0:
+ * tables [V,4], [V,4], [V,8], view v reads row v; per_view == 0: ONE row each, read by every view.  fp32 throughout, every operation
+ * unfused and in the order csrc/capture.hip writes down (the arc tangent included: range reduction and a Taylor polynomial, no library
+ * call), so capture.undistort_bank on CPU tensors gives the same bits.  V <= 65535, 1 <= H, W < 2^24, H*W < 2^31; src != dst. */
+#define N2M_LENS_BROWN 1
+#define N2M_LENS_FISHEYE 2
+typedef struct {
+    const void* src; void* dst; uint32_t V, H, W, model, depth, per_view;
+    const float* src_intrinsics; const float* out_intrinsics; const float* lens;
+} N2mUndistort;   /* HOST struct */
+int n2m_capture_undistort(const N2mUndistort* d, void* stream);
 
 /* Photometric loss head of the stage-0 step in one launch per direction:
  *   pred   = image + (1 - weights_sum) * bg                      nerf/renderer.py:747

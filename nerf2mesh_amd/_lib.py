@@ -135,6 +135,7 @@ SIGNATURES = {
     "n2m_depth_bank_fill": [_vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
     "n2m_capture_view": [_vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "n2m_capture_box_downscale": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
+    "n2m_capture_undistort": [_vp, _vp],
     "n2m_adam_step": [_vp, ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp],
     "n2m_adam_step_scaler": [_vp, ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp, _vp],
     "n2m_ema_update": [_vp, _f32, _vp],
@@ -244,6 +245,15 @@ class BatchRays(ctypes.Structure):
                 ("kp_depth", _vp), ("kp_weight", _vp), ("view", _u32), ("first", _u32), ("aabb", _vp), ("min_near", _f32), ("cam_near_far", _vp),
                 ("rays_o", _vp), ("rays_d", _vp), ("rgba", _vp), ("nears", _vp), ("fars", _vp), ("noises", _vp), ("bg", _vp), ("gt_depth", _vp),
                 ("depth_weight", _vp), ("counter", _vp)]
+
+
+LENS_BROWN, LENS_FISHEYE = 1, 2
+
+
+class Undistort(ctypes.Structure):
+    """N2mUndistort of include/n2m_hip.h."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("V", _u32), ("H", _u32), ("W", _u32), ("model", _u32), ("depth", _u32), ("per_view", _u32),
+                ("src_intrinsics", _vp), ("out_intrinsics", _vp), ("lens", _vp)]
 
 
 class CompositeLoss(ctypes.Structure):

@@ -188,7 +188,134 @@ capture_box_downscale_kernel(const uint32_t* __restrict__ src /*[V,H,W]*/, uint3
     dst[(size_t)blockIdx.y * h * w + n] = out;
 }
 
+// ---------------------------------------------------------------------------------------------- lens undistortion (capture.undistort_bank)
+// The forward lens model of COLMAP's camera models (https://colmap.github.io/cameras.html): ideal normalised (x, y), y down, -> distorted
+// normalised (xd, yd).  Mirror of capture.lens_distort_f32, operation for operation: fp32, no contraction, the order below.
+//   N2M_LENS_BROWN (row = k1, k2, p1, p2, 0...: SIMPLE_RADIAL, RADIAL, OPENCV and, all zero, the pinhole models)
+//     xx = x x, yy = y y, r2 = xx + yy, r4 = r2 r2, xy = x y, radial = k1 r2 + k2 r4
+//     xd = x + ((x radial + (p1 xy + p1 xy)) + p2 (r2 + (xx + xx)))
+//     yd = y + ((y radial + (p2 xy + p2 xy)) + p1 (r2 + (yy + yy)))
+//   N2M_LENS_FISHEYE (row = k1, k2, k3, k4, 0...: OPENCV_FISHEYE)
+//     r = sqrt(r2) (correctly rounded), theta = atan(r) by lens_atan below, t2 = theta theta, t4 = t2 t2, t6 = t4 t2, t8 = t4 t4
+//     thetad = theta (1 + (((k1 t2 + k2 t4) + k3 t6) + k4 t8)), scale = thetad / r (1 where r < 1e-8), xd = x scale, yd = y scale
+// lens_atan, r >= 0: a library atanf has no stated rounding, so the arc tangent is spelled out in +, -, *, / (each correctly rounded on
+// both sides): t = 1 / r where r > 1; z = (t - 1) / (t + 1) where t > tan(pi / 8); the Taylor series of atan to z^17 by Horner in z^2
+// (|z| <= tan(pi / 8): the first dropped term is below 3e-9); + pi / 4 where reduced; pi / 2 - (that) where inverted.
+constexpr float LENS_TAN_PI_8 = 0.41421356237309503f, LENS_PI_4 = 0.78539816339744831f, LENS_PI_2 = 1.5707963267948966f;
+
+__device__ __forceinline__ float lens_atan(float r) {
+    const bool inv = r > 1.0f;
+    const float t = inv ? 1.0f / r : r;
+    const bool red = t > LENS_TAN_PI_8;
+    const float z = red ? (t - 1.0f) / (t + 1.0f) : t;
+    const float z2 = z * z;
+    float p = (float)(1.0 / 17.0);
+    p = p * z2 - (float)(1.0 / 15.0);
+    p = p * z2 + (float)(1.0 / 13.0);
+    p = p * z2 - (float)(1.0 / 11.0);
+    p = p * z2 + (float)(1.0 / 9.0);
+    p = p * z2 - (float)(1.0 / 7.0);
+    p = p * z2 + (float)(1.0 / 5.0);
+    p = p * z2 - (float)(1.0 / 3.0);
+    p = p * z2 + 1.0f;
+    float a = p * z;
+    if (red) a = a + LENS_PI_4;
+    return inv ? LENS_PI_2 - a : a;
+}
+
+__device__ __forceinline__ void lens_distort(uint32_t model, const float4 ka, float x, float y, float& xd, float& yd) {
+    const float xx = x * x, yy = y * y, r2 = xx + yy;
+    if (model == N2M_LENS_FISHEYE) {
+        const float r = sqrtf(r2);
+        const float th = lens_atan(r);
+        const float t2 = th * th, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+        const float thd = th * (1.0f + (((ka.x * t2 + ka.y * t4) + ka.z * t6) + ka.w * t8));
+        const float scale = r < 1e-8f ? 1.0f : thd / r;
+        xd = x * scale; yd = y * scale;
+        return;
+    }
+    const float r4 = r2 * r2, xy = x * y;
+    const float radial = ka.x * r2 + ka.y * r4;
+    const float a = ka.z * xy, b = ka.w * xy;
+    xd = x + ((x * radial + (a + a)) + ka.w * (r2 + (xx + xx)));
+    yd = y + ((y * radial + (b + b)) + ka.z * (r2 + (yy + yy)));
+}
+
+// One output pixel of every view: normalised coordinates from the OUTPUT camera (pixel centre (col + 0.5, row + 0.5), the convention of
+// capture.rays_from_pixels), the lens model, the SOURCE camera: u = fx xd + cx, v = fy yd + cy (continuous, pixel c covers [c, c + 1)).
+//   colour (DEPTH = false): sx = u - 0.5, sy = v - 0.5, taps floor and floor + 1 clamped to the image, weights tx = sx - floor(sx), ty likewise; per
+//     8-bit channel top = a + (b - a) tx, bot = c + (e - c) tx, val = top + (bot - top) ty, byte = clamp(floor(val + 0.5), 0, 255).  One word load per tap.
+//   depth (DEPTH = true): the texel that contains (u, v): (floor(v), floor(u)) clamped -- never a mix of two depths.
+// A thread per output pixel, consecutive lanes on consecutive columns (the taps of a wave fall in a few lines); grid.y = view.  The
+// per-view rows are wave-uniform: three 16-byte loads (the second half of a lens row is reserved, no model here reads it).
+struct UndistortK {
+    const void* src; void* dst; uint32_t H, W, model; uint32_t stride;      // stride: 1 = tables of V rows, 0 = one row for every view
+    const float4* src_k; const float4* out_k; const float4* lens;           // [V or 1] x (1, 1, 2) float4
+};
+
+template <bool DEPTH>
+__global__ void __launch_bounds__(256) capture_undistort_kernel(const UndistortK k) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t HW = k.H * k.W;
+    if (n >= HW) return;
+    const uint32_t v = blockIdx.y, t = v * k.stride;
+    const float4 S = k.src_k[t], O = k.out_k[t], ka = k.lens[2 * t];
+    const uint32_t row = n / k.W, col = n % k.W;
+    const float i = (float)col + 0.5f, j = (float)row + 0.5f;
+    const float x = (i - O.z) / O.x, y = (j - O.w) / O.y;
+    float xd, yd;
+    lens_distort(k.model, ka, x, y, xd, yd);
+    const float u = S.x * xd + S.z, w = S.y * yd + S.w;
+    const int32_t Wm = (int32_t)k.W - 1, Hm = (int32_t)k.H - 1;
+    const size_t base = (size_t)v * HW;
+    if constexpr (DEPTH) {
+        // clamped as floats (fmaxf drops a NaN), then converted: every index is inside the plane whatever the rows hold
+        const size_t ix = (size_t)fminf(fmaxf(floorf(u), 0.0f), (float)Wm), iy = (size_t)fminf(fmaxf(floorf(w), 0.0f), (float)Hm);
+        const float* __restrict__ in = reinterpret_cast<const float*>(k.src) + base;
+        reinterpret_cast<float*>(k.dst)[base + n] = in[iy * k.W + ix];
+    } else {
+        const float sx = u - 0.5f, sy = w - 0.5f;
+        const float fx0 = floorf(sx), fy0 = floorf(sy);
+        const float tx = sx - fx0, ty = sy - fy0;
+        // clamped to [-1, size] as floats (fmaxf drops a NaN), then converted: the four taps are inside the image whatever the rows hold
+        const int32_t ix = (int32_t)fminf(fmaxf(fx0, -1.0f), (float)k.W), iy = (int32_t)fminf(fmaxf(fy0, -1.0f), (float)k.H);
+        const size_t x0 = (size_t)min(max(ix, 0), Wm), x1 = (size_t)min(ix + 1, Wm);
+        const size_t y0 = (size_t)min(max(iy, 0), Hm), y1 = (size_t)min(iy + 1, Hm);
+        const uint32_t* __restrict__ in = reinterpret_cast<const uint32_t*>(k.src) + base;
+        const uint32_t wa = in[y0 * k.W + x0], wb = in[y0 * k.W + x1], wc = in[y1 * k.W + x0], we = in[y1 * k.W + x1];
+        uint32_t out = 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float a = (float)((wa >> (8 * c)) & 255u), b = (float)((wb >> (8 * c)) & 255u);
+            const float cc = (float)((wc >> (8 * c)) & 255u), e = (float)((we >> (8 * c)) & 255u);
+            const float top = a + (b - a) * tx, bot = cc + (e - cc) * tx;
+            const float val = floorf((top + (bot - top) * ty) + 0.5f);
+            out |= (uint32_t)fminf(fmaxf(val, 0.0f), 255.0f) << (8 * c);
+        }
+        reinterpret_cast<uint32_t*>(k.dst)[base + n] = out;
+    }
+}
+
 }   // namespace
+
+extern "C" int n2m_capture_undistort(const N2mUndistort* d, void* stream) {
+    N2M_NOTNULL(d);
+    N2M_NOTNULL(d->src); N2M_NOTNULL(d->dst); N2M_NOTNULL(d->src_intrinsics); N2M_NOTNULL(d->out_intrinsics); N2M_NOTNULL(d->lens);
+    N2M_REQUIRE(d->src != d->dst, N2M_EINVAL, "capture_undistort: out of place only, src and dst are the same buffer");
+    N2M_REQUIRE(d->model == N2M_LENS_BROWN || d->model == N2M_LENS_FISHEYE, N2M_EINVAL, "capture_undistort: model must be N2M_LENS_BROWN or N2M_LENS_FISHEYE");
+    N2M_REQUIRE(d->V <= 65535u && d->H >= 1 && d->W >= 1 && d->H < (1u << 24) && d->W < (1u << 24) && (uint64_t)d->H * d->W < (1ull << 31), N2M_EINVAL,
+                "capture_undistort: need V <= 65535, 1 <= H, W < 2^24 and H*W < 2^31");
+    N2M_REQUIRE((((uintptr_t)d->src_intrinsics | (uintptr_t)d->out_intrinsics | (uintptr_t)d->lens) & 15u) == 0, N2M_EINVAL,
+                "capture_undistort: the intrinsics and lens rows must be 16-byte aligned");
+    if (d->V == 0) return 0;
+    const UndistortK k{d->src, d->dst, d->H, d->W, d->model, d->per_view ? 1u : 0u, reinterpret_cast<const float4*>(d->src_intrinsics),
+                       reinterpret_cast<const float4*>(d->out_intrinsics), reinterpret_cast<const float4*>(d->lens)};
+    const dim3 grid(n2m_ceil_div((uint64_t)d->H * d->W, 256), d->V);
+    if (d->depth) capture_undistort_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(k);
+    else capture_undistort_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(k);
+    N2M_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int n2m_batch_rays(const N2mBatchRays* d, void* stream) {
     N2M_NOTNULL(d);

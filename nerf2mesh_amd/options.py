@@ -24,6 +24,8 @@ _DEFAULTS = dict(
     data_format="nerf",            # main.py:36: "nerf" | "colmap" | "dtu" (tools/train_capture.py; capture.Capture.load_nerf / load_colmap / load_dtu)
     per_view_intrinsics=False,     # not a reference option (it always keeps intrinsics [N,4]): a COLMAP set whose images use different cameras is
                                    # loaded with one (fx, fy, cx, cy) row per view (capture.Capture.per_view_intrinsics); "dtu" implies it
+    undistort=False,               # not a reference option (it ignores lens distortion): a COLMAP set is resampled once, at load, to a pinhole camera with
+                                   # its cameras' lens coefficients (capture.Capture.load_colmap(undistort=True), n2m_capture_undistort)
     lambda_ssim=0,       # not a reference option (its structural term is LPIPS on patches, --lambda_lpips, which needs VGG weights): weight of
                          # 1 - SSIM of the whole frame in stage 1 (metrics.ssim); > 0 selects the torch-graph head of trainer.Stage1Trainer
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")

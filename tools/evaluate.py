@@ -29,6 +29,7 @@ ap.add_argument("--data", default=None, help="a captured set (default: the synth
 ap.add_argument("--data_format", choices=["nerf", "colmap", "dtu"], default="nerf")
 ap.add_argument("--split", default=None, help="held-out split of --data (default: test for nerf, val for colmap / dtu)")
 ap.add_argument("--downscale", type=int, default=1)
+ap.add_argument("--undistort", action="store_true", help="colmap: undistort the images at load with the cameras' lens coefficients (DESIGN 4.26)")
 ap.add_argument("--iters0", type=int, default=3000)
 ap.add_argument("--iters1", type=int, default=300)
 ap.add_argument("--resolution", type=int, default=256)
@@ -41,7 +42,7 @@ dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 
 opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=True, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
-                   per_view_intrinsics=args.data_format == "dtu")
+                   per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort)
 model = NeRFNetwork(opt)
 if args.data is None:
     cap, poses = None, S.make_cameras(100, seed=0)
@@ -53,7 +54,7 @@ else:
         if args.data_format == "dtu":
             return Capture.load_dtu(args.data, split=split, downscale=args.downscale, device=dev)
         if args.data_format == "colmap":
-            c = Capture.load_colmap(args.data, split=split, downscale=args.downscale, device=dev)
+            c = Capture.load_colmap(args.data, split=split, downscale=args.downscale, device=dev, undistort=args.undistort)
             c.cam_near_far = None
             return c
         return Capture.load_nerf(args.data, split=split, downscale=args.downscale, device=dev)

@@ -5,14 +5,15 @@
 
     tools/train_capture.py PATH --workspace DIR [--iters0 N --iters1 N --downscale k --scale s --bound b --color_space srgb|linear]
                            [--data_format colmap [--enable_sparse_depth | --enable_dense_depth] [--lambda_depth w] [--enable_cam_near_far] [--enable_cam_center]
-                                                 [--per_view_intrinsics]]
+                                                 [--per_view_intrinsics] [--undistort]]
                            [--data_format dtu]
 
   colmap: --scale defaults to -1 (1 / the nearest camera's distance), the model's training box is the sparse points' (update_aabb,
   main.py:234-235), --enable_cam_near_far clamps every ray to its view's keypoint depth range, --enable_sparse_depth makes one step in
   ten a depth step, --enable_dense_depth puts a depth target from PATH/depths/NAME.npy on every ray of every step, and the held-out views are the `val` split (every 8th image).
   --per_view_intrinsics accepts a reconstruction whose images use different cameras (COLMAP without --single_camera): one (fx, fy, cx, cy)
-  row per view.
+  row per view.  --undistort uses the cameras' lens coefficients (SIMPLE_RADIAL, RADIAL, OPENCV, OPENCV_FISHEYE): the bank is resampled once,
+  on the device, to a pinhole camera; without it the coefficients are ignored, as the reference does.
   dtu: every view has its own K (per-view intrinsics are implied), --scale defaults to 1, the masks supply alpha, and the held-out view is
   the `val` split (the first frame).
 
@@ -53,6 +54,7 @@ ap.add_argument("--downscale", type=int, default=1)
 ap.add_argument("--scale", type=float, default=None, help="default: 0.33 (nerf), -1 = automatic (colmap), 1 (dtu)")
 ap.add_argument("--data_format", choices=["nerf", "colmap", "dtu"], default="nerf")
 ap.add_argument("--per_view_intrinsics", action="store_true", help="colmap: one (fx, fy, cx, cy) row per view when the images' cameras differ; dtu implies it")
+ap.add_argument("--undistort", action="store_true", help="colmap: undistort the images at load with the cameras' lens coefficients (pinhole from then on)")
 ap.add_argument("--enable_sparse_depth", action="store_true")
 ap.add_argument("--enable_dense_depth", action="store_true", help="every step supervises depth from PATH/depths/NAME.npy (calibrated per view)")
 ap.add_argument("--enable_cam_near_far", action="store_true")
@@ -78,6 +80,8 @@ if dtu:
     args.per_view_intrinsics = True
 elif args.per_view_intrinsics and not colmap:
     ap.error("--per_view_intrinsics needs --data_format colmap or dtu (the nerf format states one camera)")
+if args.undistort and not colmap:
+    ap.error("--undistort needs --data_format colmap (the other formats state no lens)")
 if args.scale is None:
     args.scale = -1 if colmap else 1 if dtu else 0.33
 if not colmap and (args.enable_sparse_depth or args.enable_dense_depth or args.enable_cam_near_far or args.enable_cam_center):
@@ -99,7 +103,8 @@ def load(split):
         return Capture.load_nerf(args.path, split=split, scale=args.scale, offset=args.offset, downscale=args.downscale, linear=linear, device=dev)
     c = Capture.load_colmap(args.path, split=split, scale=args.scale, downscale=args.downscale, linear=linear,
                             enable_cam_center=args.enable_cam_center, sparse_depth=args.enable_sparse_depth and split == "train",
-                            dense_depth=args.enable_dense_depth and split == "train", device=dev, per_view_intrinsics=args.per_view_intrinsics)
+                            dense_depth=args.enable_dense_depth and split == "train", device=dev, per_view_intrinsics=args.per_view_intrinsics,
+                            undistort=args.undistort)
     if not args.enable_cam_near_far:
         c.cam_near_far = None
     return c
@@ -119,7 +124,7 @@ clock("load", t0, f"{len(cap)} training views {cap.H} x {cap.W} ({cap.nbytes / 1
 opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 1 / 256, iters=args.iters0, fused_mlp=True, scale=args.scale,
                    offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace,
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
-                   enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics,
+                   enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics, undistort=args.undistort,
                    lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf)
 model = NeRFNetwork(opt)
 if colmap:
