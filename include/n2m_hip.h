@@ -808,6 +808,13 @@ typedef struct {
     float* gt_depth; float* depth_weight; int32_t* counter;
 } N2mBatchRays;   /* HOST struct */
 int n2m_batch_rays(const N2mBatchRays* d, void* stream);
+/* The same batch as B = N / P^2 random P x P patches (--patch_size, nerf/utils.py:253-267), same descriptor: ray n is pixel (k / P, k % P)
+ * of patch p = n / P^2, k = n % P^2, so rgba [N,4] viewed as [B,P,P,4] is the patches, row-major.  The three draws of a patch come from
+ * the uniforms of its first two rays, f = p P^2: view = floor(u[f,0] V) as above, top row i0 = min(H-P-1, (uint32)(u[f,1] (float)(H-P))),
+ * left column j0 = min(W-P-1, (uint32)(u[f+1,1] (float)(W-P))) (randint(0, H - P), upper end excluded); columns 2..5 stay per ray.
+ * Intrinsics, ground truth, depth gather, clamp and counter follow the descriptor as in n2m_batch_rays.  N2M_EINVAL unless
+ * 2 <= P < min(H, W) and N % P^2 == 0; coords != NULL (keypoint batches) is N2M_EUNSUPPORTED.  All checked before the launch. */
+int n2m_batch_rays_patch(const N2mBatchRays* d, uint32_t P, void* stream);
 /* views_out [N] i32: the view each ray of the batch drawn from uniforms [N,6] reads -- column 0 through the SAME device function the
  * batch kernel uses.  Needed by the per-image appearance codes (--ind_dim, n2m_mlp.h) only; a sparse-depth batch has one view, which the
  * host knows. */
@@ -1032,6 +1039,19 @@ int n2m_ssim_forward(const float* x, const float* y, uint32_t H, uint32_t W, uin
  * with respect to y. */
 int n2m_ssim_backward(const float* x, const float* y, const float* dS, uint32_t H, uint32_t W, uint32_t C, const float* taps_host,
                       const float* g, float* grad_x, void* stream);
+/* The same SSIM for a batch of B square patches in one launch pair: x, y fp32 [B, P, P, C] contiguous, C 1 or 3, 11 <= P <= 64, B >= 1
+ * (else N2M_EINVAL; NULL pointers N2M_ENULL; both before any launch).  Per patch exactly the definition above -- a window never holds a
+ * pixel of another patch.  per_patch [B] = mean of S over the patch's (P - 10)^2 C windows; out[0] = mean over all B (P - 10)^2 C windows;
+ * dS_or_null: [B, 3, P - 10, P - 10, C], the three derivative maps per patch; partials: n2m_ssim_patches_partials(B, P) floats of scratch
+ * (one sum per workgroup = per band of window rows of a patch).  Every sum runs in a fixed order (lanes, waves, bands, patches): no
+ * float atomics, two calls give the same bits, and a patch's values do not depend on the other patches. */
+uint32_t n2m_ssim_patches_partials(uint32_t B, uint32_t P);
+int n2m_ssim_patches_forward(const float* x, const float* y, uint32_t B, uint32_t P, uint32_t C, const float* taps_host, float* dS_or_null,
+                             float* partials, float* per_patch, float* out, void* stream);
+/* grad_x[b, p] = g[0] / (B (P - 10)^2 C) * sum over windows q of patch b containing p of w(p - q) (A[q] + 2 x[p] B[q] + y[p] Cq[q]); a
+ * gather, every pixel written once.  g: DEVICE scalar.  Overwrites grad_x [B, P, P, C]; no gradient with respect to y. */
+int n2m_ssim_patches_backward(const float* x, const float* y, const float* dS, uint32_t B, uint32_t P, uint32_t C, const float* taps_host,
+                              const float* g, float* grad_x, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * per-kernel timing (measurement support for bench.py; not part of the reference surface)

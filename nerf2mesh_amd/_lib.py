@@ -131,6 +131,7 @@ SIGNATURES = {
     "n2m_freq_encode_backward": [_vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_get_rays": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "n2m_batch_rays": [_vp, _vp],
+    "n2m_batch_rays_patch": [_vp, _u32, _vp],
     "n2m_batch_views": [_vp, _u32, _u32, _vp, _vp],
     "n2m_depth_bank_fill": [_vp, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp],
     "n2m_capture_view": [_vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
@@ -150,6 +151,9 @@ SIGNATURES = {
     "n2m_ssim_partials": [_u32, _u32],                                                          # returns uint32 (RESTYPES)
     "n2m_ssim_forward": [_vp, _vp, _u32, _u32, _u32, ctypes.POINTER(_f32), _vp, _vp, _vp, _vp, _vp],
     "n2m_ssim_backward": [_vp, _vp, _vp, _u32, _u32, _u32, ctypes.POINTER(_f32), _vp, _vp, _vp],
+    "n2m_ssim_patches_partials": [_u32, _u32],                                                  # returns uint32 (RESTYPES)
+    "n2m_ssim_patches_forward": [_vp, _vp, _u32, _u32, _u32, ctypes.POINTER(_f32), _vp, _vp, _vp, _vp, _vp],
+    "n2m_ssim_patches_backward": [_vp, _vp, _vp, _u32, _u32, _u32, ctypes.POINTER(_f32), _vp, _vp, _vp],
     # include/n2m_mlp.h
     "n2m_field_forward": [_vp] * 11 + [_u32, _int, _int] + [_vp] * 4,
     "n2m_field_backward": [_vp] * 11 + [_u32, _int, _int] + [_vp] * 14,
@@ -210,7 +214,7 @@ SIGNATURES = {
     "n2m_prof_seen": [_int, ctypes.POINTER(ctypes.c_uint64)],
 }
 
-RESTYPES = {"n2m_occupancy_update_partials": _u32, "n2m_ssim_partials": _u32,"n2m_grid_binned_workspace_bytes": _u64, "n2m_grid_binned_pair_workspace_bytes": _u64, "n2m_march_fused_workspace_bytes": _u64,
+RESTYPES = {"n2m_occupancy_update_partials": _u32, "n2m_ssim_partials": _u32, "n2m_ssim_patches_partials": _u32, "n2m_grid_binned_workspace_bytes": _u64, "n2m_grid_binned_pair_workspace_bytes": _u64, "n2m_march_fused_workspace_bytes": _u64,
             "n2m_marching_cubes_workspace_bytes": _u64, "n2m_field_spec_partials": _u32, "n2m_field_ind_max_dim": _u32,
             "n2m_field_ind_workspace_bytes": _u64}   # everything else returns an int status
 

@@ -106,15 +106,19 @@ def intrinsics_row(intrinsics, view):
     return tuple(float(x) for x in intrinsics)
 
 
-def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None, dense_depth=None):
+def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None, dense_depth=None,
+                           patch_size=1):
     """synthetic.batch_from_uniforms with the ground truth gathered from a packed uint8 bank [V,H*W] and decoded through `lut`.  On the GPU
     one kernel (n2m_batch_rays, every form below one descriptor); below it the torch statement of the same arithmetic, taken on the CPU.
     dense_depth [V,H*W] fp32 (Capture.dense_depth, --enable_dense_depth): an eighth tensor gt_depth [N] = dense_depth[view_n, pixel_n]
     follows the seven (`out` then has eight entries).  intrinsics: (fx, fy, cx, cy), or the table form of a per-view set
     (Capture.intrinsics, fp32 [V,4] beside the poses): ray n takes the row of its view, with or without a depth bank; on the CPU the same
-    statement with the rows gathered at `cam`."""
+    statement with the rows gathered at `cam`.  patch_size P > 1 (--patch_size): N / P^2 random P x P patches instead of N random pixels
+    (synthetic.patch_pixels; n2m_batch_rays_patch on the GPU, the same descriptor), every output in the patches' row-major order."""
     dev = poses.device
-    N, V = u.shape[0], poses.shape[0]
+    N, V, P = u.shape[0], poses.shape[0], int(patch_size)
+    if P != 1 and (P < 2 or P >= H or P >= W or N % (P * P) != 0):
+        synthetic.patch_pixels(u, V, H, W, P)        # raises, saying which
     table = intrinsics_table(intrinsics, V, dev)
     if table is None:
         fx, fy, cx, cy = (float(x) for x in intrinsics)
@@ -133,10 +137,17 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
                            bg=L.ptr(bg), gt_depth=L.ptr(gtd), counter=L.ptr(counter))
         if table is None:
             desc.fx, desc.fy, desc.cx, desc.cy = fx, fy, cx, cy
-        L.call("n2m_batch_rays", ctypes.addressof(desc), L.stream())
+        if P != 1:
+            L.call("n2m_batch_rays_patch", ctypes.addressof(desc), P, L.stream())
+        else:
+            L.call("n2m_batch_rays", ctypes.addressof(desc), L.stream())
         return (o, d, rgba, nears, fars, noises, bg) + (() if gtd is None else (gtd,))
-    cam = (u[:, 0] * V).long().clamp(max=V - 1)
-    pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
+    if P != 1:
+        cam, row, col = synthetic.patch_pixels(u, V, H, W, P)
+        pix = row * W + col
+    else:
+        cam = (u[:, 0] * V).long().clamp(max=V - 1)
+        pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
     o, d = rays_from_pixels(poses, cam, pix % W, torch.div(pix, W, rounding_mode="floor"),
                             (fx, fy, cx, cy) if table is None else table[cam].unbind(-1))
     nears, fars = synthetic.near_far_clamped(o, d, aabb, min_near, cam_near_far, cam)
@@ -146,11 +157,21 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
     return seven if dense_depth is None else seven + (dense_depth[cam, pix],)
 
 
-def batch_views(u, V, out=None):
+def batch_views(u, V, out=None, patch_size=1):
     """int32 [N]: the view every ray of the batch drawn from the uniforms u [N,6] reads -- column 0 through the expression the batch
     kernels use (n2m_batch_views shares their device function; on the CPU the statement of batch_from_uniforms_u8).  Needed by the
-    per-image appearance codes (--ind_dim) only; a sparse-depth batch has one view: torch.full((K,), view)."""
-    N = u.shape[0]
+    per-image appearance codes (--ind_dim) only; a sparse-depth batch has one view: torch.full((K,), view).  patch_size P > 1: every ray
+    of a patch reads the view its patch's FIRST ray names (n2m_batch_rays_patch) -- that value, broadcast over the patch's P^2 rays."""
+    N, P = u.shape[0], int(patch_size)
+    if P != 1:
+        if P < 2 or N % (P * P) != 0:
+            raise ValueError(f"a patch batch holds a multiple of patch_size^2 = {P * P} rays (patch_size >= 2), got {N}")
+        per_ray = batch_views(u, V)
+        cam = per_ray.view(-1, P * P)[:, :1].expand(-1, P * P).reshape(-1)
+        if out is not None:
+            out[:N].copy_(cam)
+            return out[:N]
+        return cam.contiguous()
     if u.device.type == "cuda":
         from . import _lib as L
         if out is None:

@@ -113,6 +113,29 @@ __global__ void __launch_bounds__(256) batch_rays_kernel(const BatchRaysK k) {
     if (n == 0 && k.counter) k.counter[0] = 0;
 }
 
+// Patch mode (--patch_size P, nerf/utils.py:253-267): the batch is B = N / P^2 random P x P patches, ray n the pixel (k / P, k % P) of
+// patch p = n / P^2, k = n % P^2 (meshgrid 'ij' order: rgba [N,4] viewed as [B,P,P,4] is the patches, row-major).  The three draws of a
+// patch come from the uniforms of its first two rays, f = p P^2: the view from u[f,0] through view_of_uniform, the top row from u[f,1] over
+// H - P start rows and the left column from u[f+1,1] over W - P start columns (randint(0, H - P), upper end excluded: the last start row and
+// column are never drawn, as in the reference).  Columns 2..5 stay per ray.  Everything after the pixel choice is batch_ray.
+template <bool U8>
+__global__ void __launch_bounds__(256) batch_rays_patch_kernel(const BatchRaysK k, uint32_t P, uint32_t PP) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= k.N) return;
+    const uint32_t p = n / PP, q = n - p * PP;
+    const float* uf = k.u + (size_t)p * PP * 6;
+    const uint32_t v = view_of_uniform(uf[0], k.V);
+    const uint32_t i0 = min(k.H - P - 1u, (uint32_t)(uf[1] * (float)(k.H - P)));
+    const uint32_t j0 = min(k.W - P - 1u, (uint32_t)(uf[7] * (float)(k.W - P)));
+    float fx = k.fx, fy = k.fy, cx = k.cx, cy = k.cy;
+    if (k.intrinsics) {
+        const float4 K = k.intrinsics[v];
+        fx = K.x; fy = K.y; cx = K.z; cy = K.w;
+    }
+    batch_ray<U8>(k, n, v, j0 + q % P, i0 + q / P, fx, fy, cx, cy);
+    if (n == 0 && k.counter) k.counter[0] = 0;
+}
+
 // One view of the dense-depth bank (capture.dense_depth_fill): dst [H,W] = bilinear(src [h,w]) * scale + bias with cv2.INTER_LINEAR's
 // geometry -- source coordinate (x + 0.5) * rx - 0.5 per axis (rx = w / W, ry = h / H as the host rounded them to fp32), the two taps of
 // an axis clamped to the edge, fp32 weights, a + (b - a) * t per axis (columns first), so equal taps give their value exactly.  A thread
@@ -317,7 +340,8 @@ extern "C" int n2m_capture_undistort(const N2mUndistort* d, void* stream) {
     return 0;
 }
 
-extern "C" int n2m_batch_rays(const N2mBatchRays* d, void* stream) {
+// P == 0: the pixel / keypoint batch of n2m_batch_rays; P >= 2: the patch batch of n2m_batch_rays_patch.  One set of checks for both.
+static int batch_rays(const N2mBatchRays* d, uint32_t P, bool patch, void* stream) {
     N2M_NOTNULL(d);
     N2M_NOTNULL(d->poses); N2M_NOTNULL(d->uniforms); N2M_NOTNULL(d->aabb); N2M_NOTNULL(d->rays_o); N2M_NOTNULL(d->rays_d); N2M_NOTNULL(d->rgba);
     N2M_NOTNULL(d->nears); N2M_NOTNULL(d->fars); N2M_NOTNULL(d->noises);
@@ -339,6 +363,11 @@ extern "C" int n2m_batch_rays(const N2mBatchRays* d, void* stream) {
         N2M_REQUIRE(d->depth_bank == nullptr || u8, N2M_EUNSUPPORTED, "batch_rays: the depth gather is built beside the RGBA8 bank only");
         N2M_REQUIRE(((uintptr_t)d->intrinsics & 15u) == 0, N2M_EINVAL, "batch_rays: intrinsics [V,4] must be 16-byte aligned (one load per ray)");
     }
+    if (patch) {
+        N2M_REQUIRE(!kp, N2M_EUNSUPPORTED, "batch_rays_patch: keypoint batches (coords != NULL) have no patch mode");
+        N2M_REQUIRE(P >= 2 && P < d->H && P < d->W, N2M_EINVAL, "batch_rays_patch: need 2 <= P < H and P < W, got P = %u on %u x %u", P, d->H, d->W);
+        N2M_REQUIRE(d->N % (P * P) == 0, N2M_EINVAL, "batch_rays_patch: N = %u is not a multiple of P^2 = %u", d->N, P * P);
+    }
     if (d->N == 0) return 0;
     const BatchRaysK k{d->poses, d->uniforms, d->V, d->N, d->H, d->W, d->H * d->W, d->fx, d->fy, d->cx, d->cy,
                        reinterpret_cast<const float4*>(d->intrinsics), d->images, d->bank, d->lut, d->depth_bank,
@@ -346,12 +375,19 @@ extern "C" int n2m_batch_rays(const N2mBatchRays* d, void* stream) {
                        d->view, d->aabb, d->min_near, d->cam_near_far, d->rays_o, d->rays_d, d->rgba, d->nears, d->fars, d->noises, d->bg,
                        d->gt_depth, d->depth_weight, d->counter};
     const dim3 grid(n2m_ceil_div(d->N, 256));
-    if (kp) batch_rays_kernel<true, true><<<grid, 256, 0, (hipStream_t)stream>>>(k);
+    if (patch) {
+        if (u8) batch_rays_patch_kernel<true><<<grid, 256, 0, (hipStream_t)stream>>>(k, P, P * P);
+        else batch_rays_patch_kernel<false><<<grid, 256, 0, (hipStream_t)stream>>>(k, P, P * P);
+    } else if (kp) batch_rays_kernel<true, true><<<grid, 256, 0, (hipStream_t)stream>>>(k);
     else if (u8) batch_rays_kernel<true, false><<<grid, 256, 0, (hipStream_t)stream>>>(k);
     else batch_rays_kernel<false, false><<<grid, 256, 0, (hipStream_t)stream>>>(k);
     N2M_CHECK_LAUNCH();
     return 0;
 }
+
+extern "C" int n2m_batch_rays(const N2mBatchRays* d, void* stream) { return batch_rays(d, 0, false, stream); }
+
+extern "C" int n2m_batch_rays_patch(const N2mBatchRays* d, uint32_t P, void* stream) { return batch_rays(d, P, true, stream); }
 
 extern "C" int n2m_batch_views(const float* uniforms, uint32_t V, uint32_t N, int32_t* views_out, void* stream) {
     N2M_NOTNULL(uniforms); N2M_NOTNULL(views_out);

@@ -4,13 +4,16 @@
                             C1 = 0.01^2, C2 = 0.03^2, data range 1 -- the defaults of the structural_similarity_index_measure call in the
                             reference's commented-out SSIM meter (nerf/utils.py:351-465) -- over VALID windows only (no padded border: the
                             map of an [H, W, C] pair is [H - 10, W - 10, C]).  There is no host path: CPU tensors raise.
+  ssim_patches(pred, target)  the same SSIM over a batch of square patches [B, P, P, C] (11 <= P <= 64), every patch on its own, in one launch
+                            pair: the structural term of a stage-0 patch batch (trainer.Stage0Trainer, patch_size / lambda_patch_ssim).
   psnr(a, b)                asset.psnr, re-exported.
   evaluate_views(...)       per-view and mean PSNR / SSIM of a renderer against a capture's ground truth (the reference's eval_step
                             blends it on white, nerf/utils.py:794-811), with a renderer factory per stage's product: field_renderer (stage 0),
                             mesh_renderer (render_stage1), asset_renderer (the exported files, ExportedAsset.render).
 
 LPIPS, the reference's other meter and its only structural training term, needs VGG weights and the `lpips` package; neither is part of
-this repository, so it is not built.  `1 - ssim` is the structural term stage 1 offers instead (trainer.Stage1Trainer, lambda_ssim).
+this repository, so it is not built.  `1 - ssim` is the structural term offered instead: of the whole frame in stage 1
+(trainer.Stage1Trainer, lambda_ssim), of the batch's patches in stage 0 (trainer.Stage0Trainer, lambda_patch_ssim).
 """
 import ctypes
 
@@ -88,6 +91,62 @@ def ssim(pred, target, return_map=False, hw=None):
         raise RuntimeError("ssim: pred and target must be CUDA tensors (there is no host path)")
     mean, smap = _SSIM.apply(pred.float().contiguous(), target.detach().float().contiguous(), bool(return_map))
     return (mean, smap) if return_map else mean
+
+
+PATCH_MIN, PATCH_MAX = WINDOW, 64
+
+
+class _SSIMPatches(torch.autograd.Function):
+    """(mean, per_patch [B]) of fp32 contiguous device patches x, y [B, P, P, C]: one launch pair for the whole batch
+    (n2m_ssim_patches_forward), a workgroup per patch (or band of a patch).  The derivative maps [B, 3, P - 10, P - 10, C] are written and
+    saved only when x needs a gradient; the backward is one gather launch (n2m_ssim_patches_backward).  Only the mean is differentiable."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        B, P, _, C = x.shape
+        dev = x.device
+        need = ctx.needs_input_grad[0]
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        dS = f(B, 3, P - WINDOW + 1, P - WINDOW + 1, C) if need else None
+        partials, per_patch, out = f(L.lib().n2m_ssim_patches_partials(B, P)), f(B), f(1)
+        with torch.cuda.device(dev):
+            L.call("n2m_ssim_patches_forward", L.ptr(x), L.ptr(y), B, P, C, _TAPS, L.ptr(dS), L.ptr(partials), L.ptr(per_patch), L.ptr(out),
+                   L.stream())
+        if need:
+            ctx.save_for_backward(x, y, dS)
+        ctx.mark_non_differentiable(per_patch)
+        return out.view(()), per_patch
+
+    @staticmethod
+    def backward(ctx, g, _gpp):
+        x, y, dS = ctx.saved_tensors
+        B, P, _, C = x.shape
+        g = g.detach().to(torch.float32).reshape(1).contiguous()
+        grad = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            L.call("n2m_ssim_patches_backward", L.ptr(x), L.ptr(y), L.ptr(dS), B, P, C, _TAPS, L.ptr(g), L.ptr(grad), L.stream())
+        return grad, None
+
+
+def ssim_patches(pred, target, return_per_patch=False):
+    """Mean SSIM over a batch of square patches, every patch on its own (a window never holds a pixel of another patch): the mean of S
+    over all B (P - 10)^2 C windows as a 0-dim fp32 device tensor, differentiable in pred, not in target; with return_per_patch also the
+    [B] per-patch means (not differentiable).  pred, target: [B, P, P, C], C 1 or 3, 11 <= P <= 64, B >= 1 -- the layout of a patch batch
+    (capture.batch_from_uniforms_u8(patch_size=P)) viewed as [B, P, P, 3].  Shapes the kernel refuses raise ValueError, CPU tensors
+    RuntimeError (there is no host path)."""
+    if pred.dim() != 4 or pred.shape != target.shape or pred.shape[1] != pred.shape[2]:
+        raise ValueError(f"ssim_patches: patches must be two [B, P, P, C] tensors of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    B, P, _, C = pred.shape
+    if P < PATCH_MIN or P > PATCH_MAX:
+        raise ValueError(f"ssim_patches: P must be {PATCH_MIN} .. {PATCH_MAX}, got {P}")
+    if C not in (1, 3):
+        raise ValueError(f"ssim_patches: C must be 1 or 3, got {C}")
+    if B < 1:
+        raise ValueError("ssim_patches: B must be at least 1")
+    if not (pred.is_cuda and target.is_cuda):
+        raise RuntimeError("ssim_patches: pred and target must be CUDA tensors (there is no host path)")
+    mean, per_patch = _SSIMPatches.apply(pred.float().contiguous(), target.detach().float().contiguous())
+    return (mean, per_patch) if return_per_patch else mean
 
 
 # ------------------------------------------------------------------------------------------------ held-out evaluation

@@ -28,6 +28,9 @@ _DEFAULTS = dict(
                                    # its cameras' lens coefficients (capture.Capture.load_colmap(undistort=True), n2m_capture_undistort)
     lambda_ssim=0,       # not a reference option (its structural term is LPIPS on patches, --lambda_lpips, which needs VGG weights): weight of
                          # 1 - SSIM of the whole frame in stage 1 (metrics.ssim); > 0 selects the torch-graph head of trainer.Stage1Trainer
+    lambda_patch_ssim=0,  # not a reference option: weight of 1 - SSIM over the P x P patches of a stage-0 batch (metrics.ssim_patches); needs
+                         # patch_size >= 11 and selects the unfused loss branch of trainer.Stage0Trainer.  A name of its own: lambda_ssim is handed
+                         # to both stages' options by tools/evaluate.py and stage 0 ignores it
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")
 )
 

@@ -207,15 +207,39 @@ def near_far_clamped(o, d, aabb, min_near, cam_near_far=None, cam=None):
     return nears, fars
 
 
-def batch_from_uniforms(poses, images, u, aabb, min_near, H=LEGO_HW, W=LEGO_HW, focal=LEGO_FOCAL, out=None, counter=None, cam_near_far=None):
+def patch_pixels(u, V, H, W, P):
+    """Torch statement of the patch draws of n2m_batch_rays_patch (--patch_size, nerf/utils.py:253-267): u [N,6], N = B P^2, holds B patches
+    of P x P rays; patch p takes its view from u[f,0], its top row from u[f,1] and its left column from u[f+1,1], f = p P^2 -- the same fp32
+    products and clamps as the kernel: i0 = min(H-P-1, floor(u (H-P))) (randint(0, H - P): the last start row / column is never drawn).
+    Returns (cam, row, col), int64 [N], rays in the patch's row-major ('ij') order."""
+    N, P = u.shape[0], int(P)
+    if P < 2 or P >= H or P >= W:
+        raise ValueError(f"patch_size must be 2 .. min(H, W) - 1, got {P} on {H} x {W}")
+    if N % (P * P) != 0:
+        raise ValueError(f"a patch batch holds a multiple of patch_size^2 = {P * P} rays, got {N}")
+    first = u.reshape(-1, P * P, 6)
+    cam = (first[:, 0, 0] * V).long().clamp(max=V - 1)
+    i0 = (first[:, 0, 1] * (H - P)).long().clamp(max=H - P - 1)
+    j0 = (first[:, 1, 1] * (W - P)).long().clamp(max=W - P - 1)
+    k = torch.arange(P * P, device=u.device)
+    row = i0[:, None] + torch.div(k, P, rounding_mode="floor")[None]
+    col = j0[:, None] + (k % P)[None]
+    return cam[:, None].expand(-1, P * P).reshape(-1), row.reshape(-1), col.reshape(-1)
+
+
+def batch_from_uniforms(poses, images, u, aabb, min_near, H=LEGO_HW, W=LEGO_HW, focal=LEGO_FOCAL, out=None, counter=None, cam_near_far=None,
+                        patch_size=1):
     """A training batch from ONE tensor of uniforms u [N,6] in [0,1): view = floor(u0 V), pixel = floor(u1 H W) (N random pixels over
     random views: random_image_batch, nerf/provider.py:302-303 + nerf/utils.py:271), rays and ground truth like random_batch, near/far
     of the aabb, march jitter = u2, random background = u3..u5 (nerf/utils.py:649-652).  Returns (rays_o, rays_d, rgba, nears, fars,
     noises, bg).  On the GPU this is one kernel (n2m_batch_rays) writing into `out` (a tuple of preallocated tensors) when given; the
     torch statement below is the same arithmetic.  Both training drivers draw their batches through this function, so they consume
-    identical numbers whatever their scheduling."""
+    identical numbers whatever their scheduling.  patch_size P > 1: the batch is N / P^2 random P x P patches (patch_pixels;
+    n2m_batch_rays_patch on the GPU), rgba [N,4] viewed as [N / P^2, P, P, 4] the patches in row-major order."""
     dev = poses.device
-    N, V = u.shape[0], poses.shape[0]
+    N, V, P = u.shape[0], poses.shape[0], int(patch_size)
+    if P != 1 and (P < 2 or P >= H or P >= W or N % (P * P) != 0):
+        patch_pixels(u, V, H, W, P)        # raises, saying which
     if dev.type == "cuda":
         from . import _lib as L
         if out is None:
@@ -226,10 +250,17 @@ def batch_from_uniforms(poses, images, u, aabb, min_near, H=LEGO_HW, W=LEGO_HW, 
                            images=L.ptr(images), aabb=L.ptr(aabb), min_near=float(min_near), cam_near_far=L.ptr(cam_near_far), rays_o=L.ptr(o),
                            rays_d=L.ptr(d), rgba=L.ptr(rgba), nears=L.ptr(nears), fars=L.ptr(fars), noises=L.ptr(noises), bg=L.ptr(bg),
                            counter=L.ptr(counter))
-        L.call("n2m_batch_rays", ctypes.addressof(desc), L.stream())
+        if P != 1:
+            L.call("n2m_batch_rays_patch", ctypes.addressof(desc), P, L.stream())
+        else:
+            L.call("n2m_batch_rays", ctypes.addressof(desc), L.stream())
         return o, d, rgba, nears, fars, noises, bg
-    cam = (u[:, 0] * V).long().clamp(max=V - 1)
-    pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
+    if P != 1:
+        cam, row, col = patch_pixels(u, V, H, W, P)
+        pix = row * W + col
+    else:
+        cam = (u[:, 0] * V).long().clamp(max=V - 1)
+        pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
     o, d = rays_from_pixels(poses, cam, pix, H, W, focal)
     nears, fars = near_far_clamped(o, d, aabb, min_near, cam_near_far, cam)
     return o, d, images[cam, pix], nears, fars, u[:, 2].contiguous(), u[:, 3:6].contiguous()

@@ -135,6 +135,24 @@ class Stage0Trainer:
         self.fused_tv = True          # TV gradient folded into the density encoder's binned backward
         self._one = torch.ones((), device=device)
         self.fused_loss = True        # losses.photo_loss instead of the torch graph of nerf/utils.py:658-683
+        # --patch_size P > 1 (nerf/utils.py:253-267): a batch is max(1, num_rays // P^2) random P x P patches instead of num_rays random
+        # pixels (n2m_batch_rays_patch); sparse-depth steps stay pixel batches.  lambda_patch_ssim > 0 (not a reference option) adds
+        # lambda_patch_ssim * (1 - SSIM) over those patches (metrics.ssim_patches): it needs the blended image itself, so it selects the
+        # unfused loss branch, and patches that hold an 11 x 11 window.  The step executor carries neither (Stage0Engine.supported).
+        self.patch_size = int(getattr(opt, "patch_size", 1) or 1)
+        self.lambda_patch_ssim = float(getattr(opt, "lambda_patch_ssim", 0) or 0)
+        if self.patch_size != 1:
+            H, W = (capture.H, capture.W) if capture is not None else (synthetic.LEGO_HW, synthetic.LEGO_HW)
+            if self.patch_size < 2 or self.patch_size >= H or self.patch_size >= W:
+                raise ValueError(f"patch_size must be 1 (pixel batches) or 2 .. min(H, W) - 1, got {self.patch_size} on {H} x {W} images")
+        if self.lambda_patch_ssim > 0:
+            from .metrics import PATCH_MAX, PATCH_MIN
+            if not PATCH_MIN <= self.patch_size <= PATCH_MAX:
+                raise ValueError(f"lambda_patch_ssim > 0 needs patch_size {PATCH_MIN} .. {PATCH_MAX} (one valid 11 x 11 SSIM window per patch), "
+                                 f"got patch_size {self.patch_size}")
+            self.fused_loss = False
+        self._patch = 0               # the patch size of the batch batch() made last, 0 for a pixel batch
+        self.last_patches = None      # patch mode: (image, gt_rgb) of the last step, detached, both [B,P,P,3], blended on the step's background
         self.pipeline = True          # issue march pass 1 of the next batch one step ahead (results are identical)
         self.overlap_march = True     # ... on a second stream, next to this step's backward + optimizer kernels (single-rank path)
         self.early_march = True       # ... and already at the start of the step (A/B switch; measured equal to issuing it before the backward)
@@ -169,6 +187,7 @@ class Stage0Trainer:
             self.images = synthetic.preload_images(self.poses, self.boxes)     # nerf/provider.py:224-233 (`preload`)
         view = self.depth_schedule.next() if self.depth_schedule is not None else None
         self._depth = None
+        self._patch = 0
         if view is not None:
             from .capture import batch_sparse_u8
             u = torch.rand(cap.sparse_depth.counts[view], 6, device=self.device, generator=self.gen)
@@ -180,31 +199,44 @@ class Stage0Trainer:
             if self.ind_codes:
                 self._index = torch.full((u.shape[0],), int(view), dtype=torch.int32, device=self.device)
             return rays_o, rays_d, rgba, noises, bg
-        u = torch.rand(self.num_rays, 6, device=self.device, generator=self.gen)
+        P = self.patch_size
+        if P != 1:                                        # B = max(1, num_rays // P^2) patches; num_rays itself is left to adaptive_num_rays
+            self._patch = P
+            u = torch.rand(max(1, self.num_rays // (P * P)) * P * P, 6, device=self.device, generator=self.gen)
+        else:
+            u = torch.rand(self.num_rays, 6, device=self.device, generator=self.gen)
         if self.ind_codes:
             from .capture import batch_views
-            self._index = batch_views(u, len(cap))        # the same draw, the same expression: the views the batch kernel reads
+            self._index = batch_views(u, len(cap), patch_size=P)     # the same draw, the same expression: the views the batch kernel reads
         if self.dense_depth is not None:
             from .capture import batch_from_uniforms_u8
             rays_o, rays_d, rgba, nears, fars, noises, bg, gtd = batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, u, self.model.aabb_train,
                                                                                         self.model.min_near, cap.H, cap.W, cap.intrinsics,
-                                                                                        cam_near_far=self.cam_near_far, dense_depth=self.dense_depth)
+                                                                                        cam_near_far=self.cam_near_far, dense_depth=self.dense_depth,
+                                                                                        patch_size=P)
             self._depth = (gtd, None)
         elif cap is not None:
             from .capture import batch_from_uniforms_u8
             rays_o, rays_d, rgba, nears, fars, noises, bg = batch_from_uniforms_u8(self.poses, cap.bank, cap.lut, u, self.model.aabb_train,
                                                                                    self.model.min_near, cap.H, cap.W, cap.intrinsics,
-                                                                                   cam_near_far=self.cam_near_far)
+                                                                                   cam_near_far=self.cam_near_far, patch_size=P)
         else:
             rays_o, rays_d, rgba, nears, fars, noises, bg = synthetic.batch_from_uniforms(self.poses, self.images, u, self.model.aabb_train,
-                                                                                          self.model.min_near, cam_near_far=self.cam_near_far)
+                                                                                          self.model.min_near, cam_near_far=self.cam_near_far,
+                                                                                          patch_size=P)
         self._nears_fars = (nears, fars) if self.cam_near_far is not None else None
         return rays_o, rays_d, rgba, noises, bg
 
-    def _prepare(self):
+    def _cap_rays(self, n):
+        """adaptive_num_rays in patch mode: the sample count of a few patches swings far more than that of N pixels spread over all views
+        (a batch that mostly lands on culled space has a handful of samples), and num_points / M then asks for a batch of millions of
+        rays.  A patch batch never holds more rays than the sample target; pixel batches are left as they are."""
+        return n if self.patch_size == 1 else min(n, int(self.opt.num_points))
+
+    def _prepare(self, refresh=True):
         """Occupancy refresh (every 16th step, nerf/utils.py:1155-1156) + next batch + march pass 1 for it."""
         opt, model = self.opt, self.model
-        if self.global_step % opt.update_extra_interval == 0:
+        if refresh and self.global_step % opt.update_extra_interval == 0:
             if self.sync is not None:
                 self.sync.sync_rng_for_grid_update(self.global_step)
             model.update_extra_state()
@@ -241,9 +273,19 @@ class Stage0Trainer:
         if self._next is None:
             self._next = self._prepare()
         rays_o, rays_d, images, ticket, bg_color, noises = self._next
+        if self._patch and ticket is not None:
+            # A handful of small patches can land wholly on culled space, which N pixels spread over all views never do, and the autograd
+            # renderer needs at least one sample: such a batch is drawn again (the next draws of the same generator; no second refresh).
+            from . import raymarching
+            for _ in range(64):
+                ticket = raymarching.march_rays_train_finish(ticket)
+                if ticket[0].shape[0] > 0:
+                    break
+                rays_o, rays_d, images, ticket, bg_color, noises = self._prepare(refresh=False)
         nears_fars = self._nears_fars                      # of THIS batch (batch() sets it; the overlapped preparation below replaces it)
         depth_gt = self._depth                             # likewise: (gt_depth, depth_weight) of a depth step, else None
         index = self._index                                # likewise: the view of every ray (individual codes), else None
+        patch = self._patch                                # likewise: the patch size of a patch batch, 0 for a pixel batch
         steers = depth_gt is None or self.dense_depth is not None      # a sparse-depth step (one view's keypoints) does not steer the ray count
         self._next = None
         self.global_step += 1
@@ -265,11 +307,12 @@ class Stage0Trainer:
             # the count is back long before the host needs it, and the host stays a step tail ahead of the GPU.  Same draws from
             # the same generators in the same order as the serial schedule (bg_color above, then the batch): identical results.
             from . import raymarching
-            ticket = raymarching.march_rays_train_finish(ticket)
+            if not isinstance(ticket, tuple):
+                ticket = raymarching.march_rays_train_finish(ticket)
             M0 = ticket[0].shape[0]
             self.last_num_points = M0
             if opt.adaptive_num_rays and M0 > 0 and steers:                  # nerf/utils.py:796-797 (a sparse-depth step does not steer the ray count)
-                self.num_rays = max(1, int(round((opt.num_points / M0) * self.num_rays)))
+                self.num_rays = self._cap_rays(max(1, int(round((opt.num_points / M0) * self.num_rays))))
             adapted = True
             self._next = self._prepare_overlapped()
 
@@ -280,6 +323,12 @@ class Stage0Trainer:
         if self.fused_loss:
             # background blend + ground-truth compositing + rgb/mask MSE + mean in one kernel (nerf/utils.py:658-683)
             loss = photo_loss(out["image"], out["weights_sum"], images, bg_color, opt.lambda_rgb, self._lambda_mask())
+            if patch:
+                with torch.no_grad():                      # the pair the unfused branch below forms, kept for inspection only
+                    gt_mask = images[..., 3:]
+                    gt_rgb = images[..., :3] * gt_mask + bg_color * (1 - gt_mask)
+                    blended = out["image"] + (1 - out["weights_sum"]).unsqueeze(-1) * bg_color
+                    self.last_patches = (blended.view(-1, patch, patch, 3), gt_rgb.view(-1, patch, patch, 3))
         else:
             gt_mask = images[..., 3:]
             gt_rgb = images[..., :3] * gt_mask + bg_color * (1 - gt_mask)
@@ -287,6 +336,12 @@ class Stage0Trainer:
             if opt.lambda_mask > 0 and self._lambda_mask() > 0:
                 loss = loss + opt.lambda_mask * F.mse_loss(out["weights_sum"], gt_mask.squeeze(1), reduction="none")
             loss = loss.mean()
+            if patch:
+                image_p, gt_p = out["image"].view(-1, patch, patch, 3), gt_rgb.view(-1, patch, patch, 3)
+                self.last_patches = (image_p.detach(), gt_p.detach())
+                if self.lambda_patch_ssim > 0:             # a sparse-depth step (a pixel batch) carries no SSIM term
+                    from .metrics import ssim_patches
+                    loss = loss + self.lambda_patch_ssim * (1 - ssim_patches(image_p, gt_p))
         if depth_gt is not None:
             # nerf/utils.py:685-705; the reference adds this [N,1] term to the [N] loss and means the [N,N] broadcast, which is this mean
             from .losses import sparse_depth_loss
@@ -306,7 +361,7 @@ class Stage0Trainer:
         self.samples_seen += M
         self.rays_seen += N
         if opt.adaptive_num_rays and M > 0 and not adapted and steers:                        # nerf/utils.py:796-797
-            self.num_rays = max(1, int(round((opt.num_points / M) * self.num_rays)))
+            self.num_rays = self._cap_rays(max(1, int(round((opt.num_points / M) * self.num_rays))))
 
         # TV regulariser (nerf/utils.py:812-821 adds it to the unscaled gradients after backward).  Fast path: hand it to the
         # density encoder's backward, which folds it into its own table scatter pre-multiplied by the loss scale.

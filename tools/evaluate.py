@@ -4,6 +4,7 @@
 
     tools/evaluate.py [--iters0 N --iters1 N --views N --size S --lambda_ssim w]            the short synthetic pipeline (tools/eval_export.py's flow)
     tools/evaluate.py --data PATH [--data_format nerf|colmap|dtu] [--split test|val|...]   a captured set: trains on its train split, evaluates --split
+    tools/evaluate.py --patch_size 16 [--lambda_patch_ssim w] [--field_only]                stage 0 on patch batches (the autograd trainer)
 
 Prints one table row per view and stage, then one JSON line.  LPIPS, the reference's other meter, is not built (no VGG weights here)."""
 import argparse
@@ -37,11 +38,15 @@ ap.add_argument("--texture", type=int, default=2048)
 ap.add_argument("--views", type=int, default=8, help="held-out views")
 ap.add_argument("--size", type=int, default=400, help="synthetic: side of the held-out frames")
 ap.add_argument("--lambda_ssim", type=float, default=0.0, help="stage 1: weight of 1 - SSIM (0: the reference's loss)")
+ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P x P patches instead of random pixels (1: pixels)")
+ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size >= 11)")
+ap.add_argument("--field_only", action="store_true", help="stop after the field's evaluation (no mesh, no stage 1, no export)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 
 opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=True, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
+                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim,
                    per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort)
 model = NeRFNetwork(opt)
 if args.data is None:
@@ -66,14 +71,29 @@ else:
         model.update_aabb(cap.pts_aabb.to(dev))
 
 # ---- stage 0 -> mesh -> stage 1 -> files
-cls = Stage0Engine if cap is None or Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
+pixels = args.patch_size == 1 and args.lambda_patch_ssim == 0          # patch batches and their SSIM term are the autograd trainer's
+cls = Stage0Engine if (cap is None and pixels) or Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
 eng = cls(model, opt, poses, dev, seed=0, capture=cap)
 eng.mark_untrained()
+import time
+torch.cuda.synchronize()
+t0 = time.perf_counter()
 for _ in range(args.iters0):
     eng.train_step()
+torch.cuda.synchronize()
+ms0 = (time.perf_counter() - t0) * 1e3 / max(1, args.iters0)
+print(f"[stage 0] {args.iters0} steps ({cls.__name__}, patch_size {args.patch_size}, lambda_patch_ssim {args.lambda_patch_ssim:g}): {ms0:.3f} ms / step, "
+      f"{eng.rays_seen / max(1, args.iters0):.0f} rays / step", flush=True)
 model.eval()
 with eng.averaged_parameters():
     field = metrics.evaluate_views(metrics.field_renderer(model, held), held, views)
+if args.field_only:
+    print(f"field: mean PSNR {field['mean_psnr']:.2f}, mean SSIM {field['mean_ssim']:.4f} over {len(views)} held-out views {held.H} x {held.W}")
+    print(json.dumps({"views": views, "H": held.H, "W": held.W, "iters0": args.iters0, "patch_size": args.patch_size,
+                      "lambda_patch_ssim": args.lambda_patch_ssim, "stage0_ms_per_step": round(ms0, 4), "stage0_driver": cls.__name__,
+                      "field": {k: field[k] for k in ("psnr", "ssim", "mean_psnr", "mean_ssim")}}))
+    sys.exit(0)
+with eng.averaged_parameters():
     model.export_stage0(os.path.join(args.out, "mesh_stage0"), resolution=args.resolution, **({} if cap is None else dict(dataset=cap, clean=True, decimate=True)))
 rv, rt = export.read_ply(os.path.join(args.out, "mesh_stage0", "mesh_0.ply"))
 opt.stage, opt.iters = 1, max(args.iters1, 501)

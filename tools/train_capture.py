@@ -70,6 +70,8 @@ ap.add_argument("--texture", type=int, default=2048)
 ap.add_argument("--eval_views", type=int, default=8, help="held-out views the PSNRs are averaged over")
 ap.add_argument("--ind_dim", type=int, default=0, help="per-image appearance code width (0 = off); up to 16 runs the fused field kernels")
 ap.add_argument("--ind_num", type=int, default=500, help="code rows; at least the number of training views")
+ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P x P patches instead of random pixels (the autograd trainer)")
+ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size 11 .. 64)")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -125,7 +127,8 @@ opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 
                    offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace,
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
                    enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics, undistort=args.undistort,
-                   lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf)
+                   lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf,
+                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim)
 model = NeRFNetwork(opt)
 if colmap:
     model.to(dev)
