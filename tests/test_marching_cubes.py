@@ -40,7 +40,10 @@ def _fields():
 
 def test_case_table_two_derivations_and_the_committed_file_agree():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import gen_mc_table
+    try:
+        import gen_mc_table
+    finally:
+        sys.path.pop(0)      # tools/ must not stay in front of tests/: tools/run_parity.py would shadow tests/run_parity.py for later tests
     from oracle import marching_cubes as omc
     a, b = gen_mc_table.table(), omc.case_table()
     assert [[tuple(t) for t in c] for c in a] == [[tuple(t) for t in c] for c in b]
