@@ -856,6 +856,27 @@ typedef struct {
 } N2mUndistort;   /* HOST struct */
 int n2m_capture_undistort(const N2mUndistort* d, void* stream);
 
+/* Test mode (nerf2mesh_amd/camera_path.py, csrc/campath.hip): cameras without images, and rendered frames as the bytes that are written out.
+ *
+ * n2m_path_view: the rays of frame `frame` of a pose table [F,4,4] at pixel stride `stride` -- n2m_capture_view without the image bank:
+ * rays_o, rays_d [h*w,3] and the optional dirs [h*ssaa * w*ssaa, 3] have the bits n2m_capture_view writes for the same pose, intrinsics and
+ * size (the same operations in the same order, unfused).  frame < F, stride >= 1, 1 <= H*W < 2^24, ssaa 1..8 when dirs is given. */
+int n2m_path_view(const float* poses, uint32_t F, uint32_t frame, uint32_t H, uint32_t W, uint32_t stride, float fx, float fy, float cx,
+                  float cy, float* rays_o, float* rays_d, float* dirs, uint32_t ssaa, void* stream);
+/* One rendered frame -> the bytes the reference's Trainer.test writes (nerf/utils.py:978-986).  image [n,3] f32, depth [n] f32 (finite),
+ * n = H*W; rgb_out [n,3] u8, depth_out [n] u8 (any alignment).
+ *   rgb:   x = clamp(x, 0, 1); linear != 0: x = clamp(x < 0.0031308 ? 12.92 x : 1.055 powf(x, 0.41666) - 0.055, 0, 1) (linear_to_srgb,
+ *          nerf/utils.py:45-46); byte = (uint8)(x * 255.f), which truncates.  The clamp is a deviation: the reference lets a value above 1
+ *          wrap in astype(uint8); for values in [0, 1] the bytes are its.
+ *   depth: mn, mx = the frame's min and max; byte = (uint8)(((d - mn) / (mx - mn + 1e-6f)) * 255.f), every operation one fp32 rounding
+ *          (no contraction, correctly rounded division).  A constant frame gives zeros.
+ * Two launches: per-workgroup (min, max) pairs into `partials` [N2M_FRAME_PACK_PARTIALS, 2] f32 (device scratch, written before it is read:
+ * no initialisation, no host read), then the pack, each workgroup of which reduces those pairs again.  min and max do not depend on the
+ * order, so neither do the bytes.  With linear == 0 the result is bit for bit camera_path.frame_pack_torch on the same tensors.  n < 2^32. */
+#define N2M_FRAME_PACK_PARTIALS 256
+int n2m_frame_pack(const float* image, const float* depth, uint32_t n, int linear, uint8_t* rgb_out, uint8_t* depth_out, float* partials,
+                   void* stream);
+
 /* Photometric loss head of the stage-0 step in one launch per direction:
  *   pred   = image + (1 - weights_sum) * bg                      nerf/renderer.py:747
  *   target = gt.rgb * gt.a + bg * (1 - gt.a)                     nerf/utils.py:663-664

@@ -137,6 +137,8 @@ SIGNATURES = {
     "n2m_capture_view": [_vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "n2m_capture_box_downscale": [_vp, _u32, _u32, _u32, _u32, _vp, _vp],
     "n2m_capture_undistort": [_vp, _vp],
+    "n2m_path_view": [_vp, _u32, _u32, _u32, _u32, _u32, _f32, _f32, _f32, _f32, _vp, _vp, _vp, _u32, _vp],
+    "n2m_frame_pack": [_vp, _vp, _u32, _int, _vp, _vp, _vp, _vp],
     "n2m_adam_step": [_vp, ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp],
     "n2m_adam_step_scaler": [_vp, ctypes.c_double, ctypes.c_double, _f32, _vp, _vp, _vp, _vp, _vp],
     "n2m_ema_update": [_vp, _f32, _vp],
@@ -258,6 +260,9 @@ class Undistort(ctypes.Structure):
     """N2mUndistort of include/n2m_hip.h."""
     _fields_ = [("src", _vp), ("dst", _vp), ("V", _u32), ("H", _u32), ("W", _u32), ("model", _u32), ("depth", _u32), ("per_view", _u32),
                 ("src_intrinsics", _vp), ("out_intrinsics", _vp), ("lens", _vp)]
+
+
+FRAME_PACK_PARTIALS = 256          # N2M_FRAME_PACK_PARTIALS of include/n2m_hip.h
 
 
 class CompositeLoss(ctypes.Structure):

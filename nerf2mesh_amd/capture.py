@@ -1168,7 +1168,7 @@ class Capture:
         scale_mat)[:3,:4] in fp32, as the reference forms it; then -- cv2.decomposeProjectionMatrix is not used here -- decompose_projection
         in float64: row (K00, K11, K02, K12) of K / K22 and the pose [R^T | C], through nerf_matrix_to_ngp (scale == -1 means 1) and the
         three axis fixes of :107-109.  Every view has its own K: the set comes back in the table form unless all rows are equal.  `val` is
-        the first frame, `train` the rest, `trainval` / `all` every frame (the reference's test trajectory is not built).  downscale=k: the
+        the first frame, `train` the rest, `trainval` / `all` every frame (the reference's test trajectory: camera_path.CameraPath).  downscale=k: the
         bank's integer box mean, H // k x W // k, and the rows divided by k -- the reference resizes the images and forgets that division
         (its rays of a downscaled DTU set use the full-size K)."""
         if split not in ("train", "val", "trainval", "all"):

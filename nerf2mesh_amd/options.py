@@ -31,6 +31,7 @@ _DEFAULTS = dict(
     lambda_patch_ssim=0,  # not a reference option: weight of 1 - SSIM over the P x P patches of a stage-0 batch (metrics.ssim_patches); needs
                          # patch_size >= 11 and selects the unfused loss branch of trainer.Stage0Trainer.  A name of its own: lambda_ssim is handed
                          # to both stages' options by tools/evaluate.py and stage 0 ignores it
+    camera_traj="",      # main.py:28: the test-time camera path, "" (interpolate between random training views) | "circle" (camera_path.path_for)
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")
 )
 

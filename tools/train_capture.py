@@ -7,6 +7,7 @@
                            [--data_format colmap [--enable_sparse_depth | --enable_dense_depth] [--lambda_depth w] [--enable_cam_near_far] [--enable_cam_center]
                                                  [--per_view_intrinsics] [--undistort]]
                            [--data_format dtu]
+                           [--test [--test_no_video] [--camera_traj circle] [--n_test N]]
 
   colmap: --scale defaults to -1 (1 / the nearest camera's distance), the model's training box is the sparse points' (update_aabb,
   main.py:234-235), --enable_cam_near_far clamps every ray to its view's keypoint depth range, --enable_sparse_depth makes one step in
@@ -22,6 +23,11 @@
   -> one JSON line: held-out PSNR of both stages (the test split; without one, the training views) and evaluate_export of the written files.
      `train_loss_tail` is the mean stage-0 training loss over the last 100 steps and `ind_dim` the code width (--ind_dim): two runs of the same
      schedule and seed with --ind_dim 0 and 8 report what the per-image codes buy on a set whose exposure varies.
+
+  --test: after training, test mode (the reference's `main.py --test`): a path of cameras that are not in the set -- the
+  interpolation between 5 random training views with N + 1 frames per segment, or with --camera_traj circle the reference's circle -- is
+  rendered from the stage-1 mesh and written to WORKSPACE/results as {name}_{i:04d}_rgb.png / _depth.png, and as animated PNGs
+  ({name}_rgb.apng, {name}_depth.apng: the stand-in for the reference's mp4) unless --test_no_video.
 
 Reads nothing but PATH; writes under --workspace.  With --bound > 1 stage 1 refines the inner mesh (cascade 0) only, except under --sdf:
 `--sdf --bound 2` is the SDF recipe on an unbounded scene (contracted background), export_stage0 then writes the outer shell as mesh_1.ply
@@ -72,6 +78,10 @@ ap.add_argument("--ind_dim", type=int, default=0, help="per-image appearance cod
 ap.add_argument("--ind_num", type=int, default=500, help="code rows; at least the number of training views")
 ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P x P patches instead of random pixels (the autograd trainer)")
 ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size 11 .. 64)")
+ap.add_argument("--test", action="store_true", help="after training, render a test-time camera path from the stage-1 mesh into WORKSPACE/results")
+ap.add_argument("--test_no_video", action="store_true", help="--test: frames only, no animated PNGs")
+ap.add_argument("--camera_traj", choices=["", "circle"], default="", help="--test: the path (default: interpolate between random training views)")
+ap.add_argument("--n_test", type=int, default=24, help="--test: frames per segment of the interpolated path, less one")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -128,7 +138,7 @@ opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
                    enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics, undistort=args.undistort,
                    lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf,
-                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim)
+                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, camera_traj=args.camera_traj)
 model = NeRFNetwork(opt)
 if colmap:
     model.to(dev)
@@ -185,10 +195,20 @@ model.export_stage1(out_dir, h0=args.texture, w0=args.texture, atlas="charts")
 ev = evaluate_export(model, ExportedAsset.load(out_dir), eval_views, held.H, held.W)
 clock("export_stage1", t0, "files: " + ", ".join(sorted(os.listdir(out_dir))))
 
+test_frames = 0
+if args.test:
+    from nerf2mesh_amd import camera_path, metrics
+    t0 = time.perf_counter()
+    path = camera_path.path_for(cap, opt, n_test=args.n_test, seed=args.seed)
+    rgb, depth = camera_path.render_path(metrics.mesh_renderer(model, path), path, linear=linear)
+    camera_path.save_frames(rgb, depth, os.path.join(args.workspace, "results"), "ngp_stage1", video=None if args.test_no_video else "apng")
+    test_frames = len(path)
+    clock("test", t0, f"{test_frames} frames {path.H} x {path.W} of the {'circle' if args.camera_traj else 'interpolated'} path -> {os.path.join(args.workspace, 'results')}")
+
 depth_steps = sum(v is not None for v in eng.depth_schedule.log[:args.iters0]) if getattr(eng, "depth_schedule", None) is not None else 0
 if args.enable_dense_depth:
     depth_steps = args.iters0                  # every step carries the depth term
-print(json.dumps({"data_format": args.data_format, "ind_dim": args.ind_dim, "train_loss_tail": train_loss_tail, "per_view_intrinsics": bool(cap.per_view_intrinsics), "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
+print(json.dumps({"data_format": args.data_format, "test_frames": test_frames, "ind_dim": args.ind_dim, "train_loss_tail": train_loss_tail, "per_view_intrinsics": bool(cap.per_view_intrinsics), "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
                   "bank_mb": round(cap.nbytes / 1e6, 3), "iters0": args.iters0, "iters1": args.iters1, "faces": int(f0.shape[0]),
                   "psnr_stage0": float(np.mean(psnr0)), "psnr_stage1": float(np.mean(psnr1)), "export_psnr_vs_stage1": ev["mean"],
                   "export_psnr_per_view": ev["psnr_vs_stage1"]}))
