@@ -25,7 +25,8 @@ import os
 import numpy as np
 import torch
 
-from .capture import Capture, proj_matrix, quat_to_rotmat, rays_from_pixels, rotmat_to_quat
+from .capture import Capture, proj_matrix, rays_from_pixels
+from .colmap_model import quat_to_rotmat, rotmat_to_quat
 
 
 def slerp_rotation(R0, R1, ratio):

@@ -14,17 +14,25 @@ what COLMAP writes without --single_camera, and what every DTU scan has; the ref
 nerf/colmap_provider.py:165-182, 521, 540; nerf/dtu_provider.py:93-104, 265); H != W, fx != fy and an off-centre principal point
 are allowed.  `mvps` is built FROM those intrinsics (proj_matrix), so the rasteriser of stage 1 and the rays of stage 0 see the same
 camera; the reference's projection (nerf/provider.py:266-276) ignores cx, cy and fl_x, so off-centre its rays and its raster disagree.
+
+The lens models and the undistortion pass live in lens.py, COLMAP's binary files and the pose algebra in colmap_model.py; their public
+names are imported here by name, so `from nerf2mesh_amd.capture import ...` finds everything it always did.
 """
+import collections
 import ctypes
 import json
 import math
 import os
-import struct
 
 import numpy as np
 import torch
 
 from . import synthetic
+from .colmap_model import (COLMAP_DIRS, COLMAP_MODELS, _world_flip, center_poses, decompose_projection, quat_to_rotmat,  # noqa: F401
+                           read_colmap_cameras, read_colmap_images, read_colmap_points, rotmat_to_quat, write_colmap_cameras, write_colmap_images,
+                           write_colmap_points)
+from .lens import (LENS_BROWN, LENS_FISHEYE, LENS_MAX_ITER, LENS_STEP, ZOOM_MAX, ZOOM_TOL, as_f64, border_taps_inside, lens_distort,  # noqa: F401
+                   lens_distort_f32, lens_row, lens_undistort, undistort_bank, undistort_depth, undistort_source_f32, undistort_zoom)
 
 NEAR, FAR = 0.05, 100.0          # clip planes of mvps, as synthetic.mvp_matrix
 
@@ -106,6 +114,11 @@ def intrinsics_row(intrinsics, view):
     return tuple(float(x) for x in intrinsics)
 
 
+def _uniform_index(u, col, n):
+    """int64 [N]: column `col` of the uniforms u [N,6] as an index below n (a view, a pixel) -- the batch kernels' expression."""
+    return (u[:, col] * n).long().clamp(max=n - 1)
+
+
 def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None, dense_depth=None,
                            patch_size=1):
     """synthetic.batch_from_uniforms with the ground truth gathered from a packed uint8 bank [V,H*W] and decoded through `lut`.  On the GPU
@@ -146,8 +159,7 @@ def batch_from_uniforms_u8(poses, bank, lut, u, aabb, min_near, H, W, intrinsics
         cam, row, col = synthetic.patch_pixels(u, V, H, W, P)
         pix = row * W + col
     else:
-        cam = (u[:, 0] * V).long().clamp(max=V - 1)
-        pix = (u[:, 1] * (H * W)).long().clamp(max=H * W - 1)
+        cam, pix = _uniform_index(u, 0, V), _uniform_index(u, 1, H * W)
     o, d = rays_from_pixels(poses, cam, pix % W, torch.div(pix, W, rounding_mode="floor"),
                             (fx, fy, cx, cy) if table is None else table[cam].unbind(-1))
     nears, fars = synthetic.near_far_clamped(o, d, aabb, min_near, cam_near_far, cam)
@@ -168,21 +180,15 @@ def batch_views(u, V, out=None, patch_size=1):
             raise ValueError(f"a patch batch holds a multiple of patch_size^2 = {P * P} rays (patch_size >= 2), got {N}")
         per_ray = batch_views(u, V)
         cam = per_ray.view(-1, P * P)[:, :1].expand(-1, P * P).reshape(-1)
-        if out is not None:
-            out[:N].copy_(cam)
-            return out[:N]
-        return cam.contiguous()
+        return cam.contiguous() if out is None else out[:N].copy_(cam)
     if u.device.type == "cuda":
         from . import _lib as L
         if out is None:
             out = torch.empty(N, dtype=torch.int32, device=u.device)
         L.call("n2m_batch_views", L.ptr(u), int(V), N, L.ptr(out), L.stream())
         return out[:N]
-    cam = (u[:, 0] * V).long().clamp(max=V - 1).to(torch.int32)
-    if out is not None:
-        out[:N].copy_(cam)
-        return out[:N]
-    return cam
+    cam = _uniform_index(u, 0, V).to(torch.int32)
+    return cam if out is None else out[:N].copy_(cam)
 
 
 def batch_sparse_u8(poses, bank, lut, u, view, sparse_depth, aabb, min_near, H, W, intrinsics, out=None, counter=None, cam_near_far=None):
@@ -252,10 +258,7 @@ def dense_depth_fill(src, H, W, scale=1.0, bias=0.0, out=None):
     jj, ii = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
     s32, b32 = torch.tensor(float(scale), dtype=torch.float32), torch.tensor(float(bias), dtype=torch.float32)
     val = resize_linear_at(src.contiguous(), H, W, jj.reshape(-1), ii.reshape(-1)) * s32 + b32
-    if out is not None:
-        out.copy_(val)
-        return out
-    return val
+    return val if out is None else out.copy_(val)
 
 
 def fit_scale_bias(x, y, w):
@@ -360,180 +363,31 @@ def dense_depth_for(capture, opt):
     return capture.dense_depth
 
 
-# --------------------------------------------------------------------------------------------- COLMAP binary models
-# Written from COLMAP's published format description (https://colmap.github.io/format.html, "Binary File Format"; the camera model ids and
-# their parameter counts are those of src/colmap/sensor/models.h), little endian throughout:
-#   cameras.bin   u64 count; per camera: i32 id, i32 model, u64 width, u64 height, f64 params[n(model)]
-#   images.bin    u64 count; per image: i32 id, f64 q[4] (w, x, y, z), f64 t[3], i32 camera id, name (zero-terminated), u64 n2d,
-#                 n2d x (f64 x, f64 y, i64 point3D id or -1)
-#   points3D.bin  u64 count; per point: u64 id, f64 xyz[3], u8 rgb[3], f64 error, u64 track length, length x (i32 image id, i32 point2D idx)
-COLMAP_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8),
-                 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4), 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
-COLMAP_DIRS = (("colmap_sparse", "0"), ("sparse", "0"), ("colmap",))
-
-
-class _Reader:
-    def __init__(self, name):
-        with open(name, "rb") as f:
-            self.buf, self.pos, self.name = f.read(), 0, name
-
-    def take(self, fmt):
-        n = struct.calcsize(fmt)
-        if self.pos + n > len(self.buf):
-            raise ValueError(f"{self.name}: truncated at byte {self.pos}")
-        out = struct.unpack_from(fmt, self.buf, self.pos)
-        self.pos += n
-        return out
-
-    def array(self, dtype, count):
-        dt = np.dtype(dtype)
-        if self.pos + dt.itemsize * count > len(self.buf):
-            raise ValueError(f"{self.name}: truncated at byte {self.pos}")
-        out = np.frombuffer(self.buf, dt, count, self.pos)
-        self.pos += dt.itemsize * count
-        return out
-
-    def cstring(self):
-        end = self.buf.find(b"\0", self.pos)
-        if end < 0:
-            raise ValueError(f"{self.name}: unterminated name at byte {self.pos}")
-        out = self.buf[self.pos:end].decode()
-        self.pos = end + 1
-        return out
-
-
-def read_colmap_cameras(name):
-    """{camera id: dict(model, width, height, params [n] f64)}."""
-    r = _Reader(name)
-    cams = {}
-    for _ in range(r.take("<Q")[0]):
-        cid, model, w, h = r.take("<iiQQ")
-        if model not in COLMAP_MODELS:
-            raise ValueError(f"{name}: unknown camera model id {model}")
-        mname, npar = COLMAP_MODELS[model]
-        cams[cid] = dict(model=mname, width=int(w), height=int(h), params=r.array("<f8", npar).copy())
-    return cams
-
-
-def read_colmap_images(name):
-    """{image id: dict(q [4] (w, x, y, z), t [3], camera_id, name, xys [n,2] f64, point3D_ids [n] i64)}."""
-    r = _Reader(name)
-    rec = np.dtype([("xy", "<f8", 2), ("id", "<i8")])
-    ims = {}
-    for _ in range(r.take("<Q")[0]):
-        iid = r.take("<i")[0]
-        qt = r.array("<f8", 7).copy()
-        cam = r.take("<i")[0]
-        fname = r.cstring()
-        p2d = r.array(rec, r.take("<Q")[0])
-        ims[iid] = dict(q=qt[:4], t=qt[4:], camera_id=cam, name=fname, xys=p2d["xy"].copy().reshape(-1, 2), point3D_ids=p2d["id"].copy())
-    return ims
-
-
-def read_colmap_points(name):
-    """(ids [M] i64 ascending, xyz [M,3] f64, error [M] f64)."""
-    r = _Reader(name)
-    ids, xyz, err = [], [], []
-    for _ in range(r.take("<Q")[0]):
-        pid, x, y, z, _r, _g, _b, e, track = r.take("<QdddBBBdQ")
-        r.array("<i4", 2 * track)
-        ids.append(pid); xyz.append((x, y, z)); err.append(e)
-    order = np.argsort(np.asarray(ids, dtype=np.int64), kind="stable")
-    return (np.asarray(ids, dtype=np.int64)[order], np.asarray(xyz, dtype=np.float64).reshape(-1, 3)[order],
-            np.asarray(err, dtype=np.float64)[order])
-
-
-def quat_to_rotmat(q):
-    """Rotation matrix of a unit quaternion (w, x, y, z)."""
-    w, x, y, z = (float(a) for a in q)
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]], dtype=np.float64)
-
-
-def rotmat_to_quat(R):
-    """Unit quaternion (w, x, y, z), w >= 0, of a rotation matrix (the branch with the largest pivot)."""
-    t = R[0, 0] + R[1, 1] + R[2, 2]
-    if t > 0:
-        s = math.sqrt(t + 1.0) * 2
-        q = (0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s)
-    elif R[0, 0] > R[1, 1] and R[0, 0] > R[2, 2]:
-        s = math.sqrt(1.0 + R[0, 0] - R[1, 1] - R[2, 2]) * 2
-        q = ((R[2, 1] - R[1, 2]) / s, 0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s)
-    elif R[1, 1] > R[2, 2]:
-        s = math.sqrt(1.0 + R[1, 1] - R[0, 0] - R[2, 2]) * 2
-        q = ((R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s)
-    else:
-        s = math.sqrt(1.0 + R[2, 2] - R[0, 0] - R[1, 1]) * 2
-        q = ((R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s)
-    q = np.asarray(q, dtype=np.float64)
-    q /= np.linalg.norm(q)
-    return -q if q[0] < 0 else q
-
-
-def decompose_projection(P):
-    """P [3,4] = s K [R | -R C] (any scale s, either sign) -> K [3,3] upper triangular with a positive diagonal and K[2,2] = 1, R [3,3]
-    world-to-camera with det R = +1, C [3] the camera centre; float64 throughout.  What nerf/dtu_provider.py:49-63 takes from
-    cv2.decomposeProjectionMatrix, by an RQ decomposition of M = P[:,:3] (a QR factorisation of the row-reversed transpose); the signs are
-    fixed afterwards: columns of K / rows of R flipped until K's diagonal is positive, and R negated when its determinant is -1 (that
-    is P -> -P, the same camera).  C = -inv(M) P[:,3] does not depend on either."""
-    P = np.asarray(P, dtype=np.float64)
-    M = P[:3, :3]
-    J = np.eye(3)[::-1]
-    q, r = np.linalg.qr((J @ M).T)                 # J M = r^T q^T  ->  M = (J r^T J) (J q^T)
-    K, R = J @ r.T @ J, J @ q.T
-    S = np.diag(np.where(np.diag(K) < 0, -1.0, 1.0))
-    K, R = K @ S, S @ R
-    if np.linalg.det(R) < 0:
-        R = -R
-    C = -np.linalg.solve(M, P[:3, 3])
-    return K / K[2, 2], R, C
-
-
-def _rotation_between(a, b):
-    """The rotation that takes direction a to direction b (Rodrigues; nerf/colmap_provider.py:18-27 `rotmat`, whose random retry for
-    opposite directions is replaced by a fixed perpendicular axis)."""
-    a, b = a / np.linalg.norm(a), b / np.linalg.norm(b)
-    v, c = np.cross(a, b), float(np.dot(a, b))
-    if c < -1 + 1e-10:
-        axis = np.cross(a, [1.0, 0.0, 0.0] if abs(a[0]) < 0.9 else [0.0, 1.0, 0.0])
-        axis /= np.linalg.norm(axis)
-        return 2 * np.outer(axis, axis) - np.eye(3)
-    s = np.linalg.norm(v)
-    k = np.array([[0, -v[2], v[1]], [v[2], 0, -v[0]], [-v[1], v[0], 0]])
-    return np.eye(3) + k + k.dot(k) * ((1 - c) / (s ** 2 + 1e-10))
-
-
-def center_poses(poses, pts3d, enable_cam_center=False):
-    """nerf/colmap_provider.py:30-54: move the point centroid (or the camera centroid) to the origin and rotate the mean of the cameras'
-    second axis onto +z.  poses [V,4,4], pts3d [M,3], float64; returns new arrays."""
-    center = poses[:, :3, 3].mean(0) if enable_cam_center else pts3d.mean(0)
-    up = poses[:, :3, 1].mean(0)
-    R = np.eye(4)
-    R[:3, :3] = _rotation_between(up / (np.linalg.norm(up) + 1e-10), np.array([0.0, 0.0, 1.0]))
-    poses = poses.copy()
-    poses[:, :3, 3] -= center
-    return R @ poses, (pts3d - center) @ R[:3, :3].T
-
-
-def _world_flip(poses, pts):
-    """The convention change of nerf/colmap_provider.py:205-211, its own inverse on the world side: camera axes y, z negated (OpenCV ->
-    OpenGL), world (x, y, z) -> (y, x, -z) for poses and points."""
-    poses = poses.copy()
-    poses[:, :3, 1:3] *= -1
-    poses = poses[:, [1, 0, 2, 3], :]
-    poses[:, 2] *= -1
-    pts = pts[:, [1, 0, 2]].copy()
-    pts[:, 2] *= -1
-    return poses, pts
-
-
 def _read_image(name):
     from PIL import Image
     with Image.open(name) as im:
         if im.mode not in ("RGB", "RGBA"):
             im = im.convert("RGBA" if "A" in im.getbands() or "transparency" in im.info else "RGB")
         return np.asarray(im, dtype=np.uint8)
+
+
+def _read_images(pairs, require_mask):
+    """The uint8 images of (image file, mask file) pairs, a mask's first channel as the alpha.  A missing mask: FileNotFoundError with
+    require_mask; else that view is opaque, and every image is padded to four channels when any has a mask."""
+    images = []
+    for iname, mname in pairs:
+        im = _read_image(iname)
+        if os.path.exists(mname):
+            mk = _read_image(mname)
+            if mk.shape[:2] != im.shape[:2]:
+                raise ValueError(f"{mname} is {mk.shape[0]} x {mk.shape[1]}, its image {im.shape[0]} x {im.shape[1]}")
+            im = np.concatenate([im[..., :3], mk[..., :1]], -1)
+        elif require_mask:
+            raise FileNotFoundError(f"image/{os.path.basename(iname)} has no mask: {mname} is missing")
+        images.append(im)
+    if any(im.shape[-1] == 4 for im in images):
+        images = [im if im.shape[-1] == 4 else np.concatenate([im, np.full_like(im[..., :1], 255)], -1) for im in images]
+    return images
 
 
 def box_downscale(bank, H, W, k):
@@ -551,264 +405,167 @@ def box_downscale(bank, H, W, k):
     return m.contiguous().view(V, h * w, 4).view(torch.int32).view(V, h * w)
 
 
-# --------------------------------------------------------------------------------------------- lens models and undistortion
-# COLMAP's camera models as its documentation defines them (https://colmap.github.io/cameras.html; parameter order as in cameras.bin, see
-# COLMAP_MODELS): normalised image coordinates (x, y) = ((u - cx) / fx, (v - cy) / fy), y DOWN, of the ideal pinhole projection are mapped
-# forward to the distorted (xd, yd) the sensor recorded; r2 = x^2 + y^2:
-#   SIMPLE_RADIAL (f, cx, cy, k)                    xd = x (1 + k r2)                                        yd likewise
-#   RADIAL        (f, cx, cy, k1, k2)               xd = x (1 + k1 r2 + k2 r2^2)
-#   OPENCV        (fx, fy, cx, cy, k1, k2, p1, p2)  xd = x (1 + k1 r2 + k2 r2^2) + 2 p1 x y + p2 (r2 + 2 x^2)
-#                                                   yd = y (1 + k1 r2 + k2 r2^2) + 2 p2 x y + p1 (r2 + 2 y^2)
-#   OPENCV_FISHEYE (fx, fy, cx, cy, k1, k2, k3, k4) theta = atan(r), thetad = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
-#                                                   xd = x thetad / r (x itself at r = 0)
-# The first three are ONE family here (LENS_BROWN, row = k1, k2, p1, p2 with the unused entries 0; the pinhole models are its all-zero row),
-# the fisheye polynomial the other (LENS_FISHEYE, row = k1, k2, k3, k4); a row has 8 entries, the last four reserved.  Float64 numpy on
-# the host (lens_distort, its inverse lens_undistort, the zoom rule); the fp32 statement of the device function of csrc/capture.hip is
-# lens_distort_f32, operation for operation.
-LENS_BROWN, LENS_FISHEYE = 1, 2            # N2M_LENS_* of include/n2m_hip.h
-LENS_MAX_ITER, LENS_STEP = 100, 1e-12      # the inverse: at most 100 Newton steps, converged when the step is below 1e-12 (normalised units)
-ZOOM_MAX, ZOOM_TOL = 4.0, 1e-6
+# ------------------------------------------------------------------------------- the stages of Capture.load_colmap (its docstring has the rules)
+_Cameras = collections.namedtuple("_Cameras", "h0 w0 H W per_view intrinsics family src_rows out_rows lens_rows zooms")
 
 
-def lens_row(model, params):
-    """COLMAP camera `model` (name) with its parameter vector -> ((fx, fy, cx, cy), family, row [8] float64).  FULL_OPENCV, FOV and the
-    thin-prism / other fisheye models: ValueError."""
-    p = [float(x) for x in params]
-    row = np.zeros(8)
-    if model in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL", "RADIAL"):
-        f4 = (p[0], p[0], p[1], p[2])
-        row[:len(p) - 3] = p[3:]
-    elif model in ("PINHOLE", "OPENCV", "OPENCV_FISHEYE"):
-        f4 = tuple(p[:4])
-        row[:len(p) - 4] = p[4:]
-    else:
-        raise ValueError(f"unsupported COLMAP camera model: {model}")
-    return f4, (LENS_FISHEYE if model == "OPENCV_FISHEYE" else LENS_BROWN), row
+def _colmap_model(path, downscale):
+    """Locates and reads the model: cameras, images, (point ids, xyz, errors), the image folder, whether it is images_{downscale}, and the
+    sorted keys of the images that have a file in it."""
+    root = next((os.path.join(path, *c) for c in COLMAP_DIRS if os.path.exists(os.path.join(path, *c))), None)
+    if root is None:
+        raise ValueError(f"no COLMAP model under {path} (colmap_sparse/0, sparse/0, colmap)")
+    cams = read_colmap_cameras(os.path.join(root, "cameras.bin"))
+    ims = read_colmap_images(os.path.join(root, "images.bin"))
+    points = read_colmap_points(os.path.join(root, "points3D.bin"))
+    if len(points[0]) == 0:
+        raise ValueError(f"{root}: the reconstruction has no 3D points")
+    folder = os.path.join(path, f"images_{downscale}")
+    own_folder = os.path.exists(folder)
+    if not own_folder:
+        folder = os.path.join(path, "images")
+    keys = [k for k in sorted(ims) if os.path.exists(os.path.join(folder, os.path.basename(ims[k]["name"])))]
+    if not keys:
+        raise FileNotFoundError(f"{root}/images.bin lists no image that exists under {folder}")
+    return cams, ims, points, folder, own_folder, keys
 
 
-def lens_distort(family, row, x, y):
-    """Forward map, float64: ideal normalised (x, y) -> distorted (xd, yd); arrays of one shape (or numbers), row [8] as lens_row."""
-    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
-    k = [float(a) for a in row]
-    r2 = x * x + y * y
-    if family == LENS_FISHEYE:
-        r = np.sqrt(r2)
-        th = np.arctan(r)
-        t2 = th * th
-        thd = th * (1 + k[0] * t2 + k[1] * t2 ** 2 + k[2] * t2 ** 3 + k[3] * t2 ** 4)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            scale = np.where(r < 1e-8, 1.0, thd / r)
-        return x * scale, y * scale
-    if family != LENS_BROWN:
-        raise ValueError(f"unknown lens family {family}")
-    radial = k[0] * r2 + k[1] * r2 * r2
-    return (x + x * radial + 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x),
-            y + y * radial + 2 * k[3] * x * y + k[2] * (r2 + 2 * y * y))
+def _colmap_cameras(cams, cam_ids, undistort, per_view_intrinsics, ds):
+    """The cameras of the kept images (cam_ids: one id per image): full and stored image size, the intrinsics at the stored size ((fx, fy, cx,
+    cy), or [V,4] when they differ: per_view) and, with coefficients to undistort, the family and per image the rows and the zoom (else None)."""
+    used = sorted(set(cam_ids))
+    intr, lens = [], []
+    for c in used:
+        model = cams[c]["model"]
+        if not undistort and model in ("RADIAL", "OPENCV_FISHEYE"):         # accepted for the undistortion pass only
+            raise ValueError(f"unsupported COLMAP camera model: {model}")
+        f4, fam, row = lens_row(model, cams[c]["params"])
+        if undistort:                                                       # without it the coefficients are ignored
+            lens.append((fam,) + tuple(row))
+        intr.append((cams[c]["height"], cams[c]["width"]) + f4)
+    # the lens of the set: rows with a coefficient share one family; none has one -> no pass at all
+    family = None
+    if any(any(l[1:]) for l in lens):
+        fams = {l[0] for l in lens if any(l[1:])}
+        if len(fams) != 1:
+            raise ValueError("the kept images mix fisheye and polynomial lens models; a set is undistorted with one model family")
+        family = fams.pop()
+        intr = [i + l[1:] for i, l in zip(intr, lens)]             # cameras that differ in their lens alone are different cameras
+    per_view = any(i != intr[0] for i in intr[1:])
+    if per_view and not per_view_intrinsics:
+        raise ValueError(f"the kept images use {len(used)} cameras with different parameters; a Capture holds one camera model per set "
+                         "unless it is loaded with per_view_intrinsics=True (tools/train_capture.py --per_view_intrinsics)")
+    if any(i[:2] != intr[0][:2] for i in intr[1:]):
+        raise ValueError(f"the kept images use cameras of differing image sizes ({sorted({i[:2] for i in intr})} as height x width); "
+                         "per-view intrinsics still need one image size per set")
+    by_id = dict(zip(used, intr))
+    h0, w0 = intr[0][:2]
+    H, W = int(round(h0 / ds)), int(round(w0 / ds))
+    fx, fy, cx, cy = (x / ds for x in intr[0][2:6])
+    src_rows = np.array([by_id[c][2:6] for c in cam_ids], dtype=np.float64) / ds
+    if family is None:
+        return _Cameras(h0, w0, H, W, per_view, src_rows if per_view else (fx, fy, cx, cy), None, None, None, None, None)
+    # per kept image: its lens row, its source intrinsics at the bank's size, and the zoom of its camera (one bisection per camera)
+    lens_rows = np.array([by_id[c][6:] for c in cam_ids], dtype=np.float64)
+    zoom_of = {c: undistort_zoom(H, W, np.asarray(by_id[c][2:6]) / ds, family, by_id[c][6:], name=f"camera {c}") for c in used}
+    zooms = np.array([zoom_of[c] for c in cam_ids], dtype=np.float64)
+    out_rows = src_rows * np.stack([zooms, zooms, np.ones_like(zooms), np.ones_like(zooms)], -1)
+    return _Cameras(h0, w0, H, W, per_view, out_rows if per_view else (out_rows[0, 0], out_rows[0, 1], cx, cy), family, src_rows, out_rows,
+                    lens_rows, zooms)
 
 
-def lens_undistort(family, row, xd, yd):
-    """Inverse map, float64: distorted normalised (xd, yd) -> ideal (x, y), by Newton's method from (xd, yd) -- on the two coordinates with
-    the analytic Jacobian for LENS_BROWN, on theta alone for LENS_FISHEYE (then r = tan theta).  Every point is iterated until the largest
-    step of the array, in normalised units, is below LENS_STEP; more than LENS_MAX_ITER steps, or a step that is not finite: ValueError."""
-    xd, yd = np.asarray(xd, dtype=np.float64), np.asarray(yd, dtype=np.float64)
-    k = [float(a) for a in row]
-    if family == LENS_FISHEYE:
-        rd = np.sqrt(xd * xd + yd * yd)
-        th = rd.copy()
-        for _ in range(LENS_MAX_ITER):
-            t2 = th * th
-            g = th * (1 + k[0] * t2 + k[1] * t2 ** 2 + k[2] * t2 ** 3 + k[3] * t2 ** 4) - rd
-            dg = 1 + 3 * k[0] * t2 + 5 * k[1] * t2 ** 2 + 7 * k[2] * t2 ** 3 + 9 * k[3] * t2 ** 4
-            with np.errstate(all="ignore"):
-                step = g / dg
-                th = th - step
-                size = np.abs(step) * (1 + np.tan(th) ** 2)            # the step of r = tan theta
-            if not np.isfinite(size).all() or (np.abs(th) >= np.pi / 2).any():
-                break
-            if size.max(initial=0.0) < LENS_STEP:
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    scale = np.where(rd < 1e-8, 1.0, np.tan(th) / rd)
-                return xd * scale, yd * scale
-        raise ValueError("lens_undistort: the fisheye inverse did not converge (a point beyond the model's field of view?)")
-    if family != LENS_BROWN:
-        raise ValueError(f"unknown lens family {family}")
-    k1, k2, p1, p2 = k[:4]
-    x, y = xd.copy(), yd.copy()
-    for _ in range(LENS_MAX_ITER):
-        xx, yy, xy = x * x, y * y, x * y
-        r2 = xx + yy
-        radial, dr = k1 * r2 + k2 * r2 * r2, k1 + 2 * k2 * r2            # radial and d radial / d r2
-        fx_ = x + x * radial + 2 * p1 * xy + p2 * (r2 + 2 * xx) - xd
-        fy_ = y + y * radial + 2 * p2 * xy + p1 * (r2 + 2 * yy) - yd
-        a = 1 + radial + 2 * xx * dr + 2 * p1 * y + 6 * p2 * x
-        b = 2 * xy * dr + 2 * p1 * x + 2 * p2 * y
-        d = 1 + radial + 2 * yy * dr + 2 * p2 * x + 6 * p1 * y
-        det = a * d - b * b
-        with np.errstate(all="ignore"):
-            sx, sy = (d * fx_ - b * fy_) / det, (a * fy_ - b * fx_) / det
-        size = np.maximum(np.abs(sx), np.abs(sy))
-        if not np.isfinite(size).all():
-            break
-        x, y = x - sx, y - sy
-        if size.max(initial=0.0) < LENS_STEP:
-            return x, y
-    raise ValueError("lens_undistort: Newton's method did not converge (a point outside the range where the lens model is invertible?)")
+def _colmap_poses(ims, keys, pts3d, enable_cam_center, scale):
+    """Camera-to-world poses inv([R|t]) = [R^T | -R^T t] of the kept images and the points, centred, flipped and scaled: poses [V,4,4] and
+    points [M,3] float64, the scale (1 / min |camera position| for -1) and the points' box [6] fp32."""
+    poses = np.tile(np.eye(4), (len(keys), 1, 1))
+    for n, k in enumerate(keys):
+        R = quat_to_rotmat(ims[k]["q"])
+        poses[n, :3, :3] = R.T
+        poses[n, :3, 3] = -R.T @ ims[k]["t"]
+    poses, pts = center_poses(poses, pts3d, enable_cam_center)
+    poses, pts = _world_flip(poses, pts)
+    if scale == -1:
+        scale = 1.0 / np.linalg.norm(poses[:, :3, 3], axis=-1).min()
+    poses[:, :3, 3] *= scale
+    pts = pts * scale
+    return poses, pts, scale, np.concatenate([pts.min(0), pts.max(0)]).astype(np.float32)
 
 
-def _border_pixels(H, W):
-    """(rows, cols) of the 2 (H + W) - 4 border pixels of an H x W image (all of them for H or W below 3)."""
-    jj, ii = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
-    m = (jj == 0) | (jj == H - 1) | (ii == 0) | (ii == W - 1)
-    return jj[m], ii[m]
+def _colmap_keypoints(ims, keys, cam, ds, poses, pts, pids, perr, keep_model):
+    """Per kept image: with keep_model its (undistorted) keypoints (xy, index into the sorted points or -1); of those with a 3D point inside
+    the full-size frame (rounded (row, col) at the stored size, depth fp32, weight fp32, depth, weight); and the (min, max) depth."""
+    mean_err = perr.mean()
+    cnf, tab, kps = [], [], []
+    for n, k in enumerate(keys):
+        xy, ids = ims[k]["xys"], ims[k]["point3D_ids"]
+        if cam.family is not None and len(xy):
+            # distorted full-size pixels -> normalised -> ideal (host inverse) -> pixels of the zoomed camera, still at full size
+            sfx, sfy, scx, scy = cam.src_rows[n] * ds
+            try:
+                ux, uy = lens_undistort(cam.family, cam.lens_rows[n], (xy[:, 0] - scx) / sfx, (xy[:, 1] - scy) / sfy)
+            except ValueError as e:
+                raise ValueError(f"image {ims[k]['name']}: {e}") from None
+            xy = np.stack([cam.zooms[n] * sfx * ux + scx, cam.zooms[n] * sfy * uy + scy], -1)
+        if keep_model:
+            found = np.searchsorted(pids, ids).clip(0, len(pids) - 1)
+            kps.append((xy, np.where((ids != -1) & (pids[found] == ids), found, -1)))       # as indices into the sorted point list
+        rowcol = np.stack([xy[:, 1], xy[:, 0]], -1)
+        m = (ids != -1) & (rowcol[:, 0] >= 0) & (rowcol[:, 0] < cam.h0) & (rowcol[:, 1] >= 0) & (rowcol[:, 1] < cam.w0)
+        if not m.any():
+            raise ValueError(f"image {ims[k]['name']} has no keypoint with a 3D point inside the image")
+        at = np.searchsorted(pids, ids[m])
+        if (at >= len(pids)).any() or (pids[np.minimum(at, len(pids) - 1)] != ids[m]).any():
+            raise ValueError(f"image {ims[k]['name']} refers to a 3D point that points3D.bin does not hold")
+        rc = np.round(rowcol[m] / ds).astype(np.int32)
+        rc[:, 0] = rc[:, 0].clip(0, cam.H - 1)
+        rc[:, 1] = rc[:, 1].clip(0, cam.W - 1)
+        P = poses[n]
+        depth = (P[:3, 3] - pts[at]) @ P[:3, 2]
+        weight = 2 * np.exp(-(perr[at] / mean_err) ** 2)
+        cnf.append([depth.min(), depth.max()])
+        tab.append((rc, depth.astype(np.float32), weight.astype(np.float32), depth, weight))
+    return kps, tab, np.asarray(cnf, dtype=np.float32)
 
 
-def border_taps_inside(H, W, intrinsics, family, row, zoom):
-    """True when, for the output camera (zoom fx, zoom fy, cx, cy), the bilinear sample point of every border pixel centre lies inside the
-    hull of the source pixel centres, 0 <= sx <= W - 1 and 0 <= sy <= H - 1 -- then all four taps of every output pixel that carry weight
-    are source pixels.  Float64."""
-    fx, fy, cx, cy = (float(a) for a in intrinsics)
-    jj, ii = _border_pixels(H, W)
-    xd, yd = lens_distort(family, row, (ii + 0.5 - cx) / (zoom * fx), (jj + 0.5 - cy) / (zoom * fy))
-    sx, sy = fx * xd + cx - 0.5, fy * yd + cy - 0.5
-    return bool(((sx >= 0) & (sx <= W - 1) & (sy >= 0) & (sy <= H - 1)).all())
+def _split(n, split):
+    """The indices of a split of n kept images: every 8th is `val`, `train` the rest, `trainval` all."""
+    sel = list(range(n))
+    sel = sel[::8] if split == "val" else [i for i in sel if i % 8 != 0] if split == "train" else sel
+    if not sel:
+        raise ValueError(f"the {split} split of {n} images is empty")
+    return sel
 
 
-def undistort_zoom(H, W, intrinsics, family, row, name="camera"):
-    """The zoom s >= 1 of the output camera of an undistorted set (size, cx, cy kept; fx, fy multiplied by s): the smallest for which
-    border_taps_inside holds, so no output pixel is blank.  1 when all coefficients are 0 or when it holds at 1 (barrel distortion);
-    otherwise bisection on [1, ZOOM_MAX] until the bracket is below ZOOM_TOL, and its upper (holding) end is returned; ValueError naming
-    the camera when it does not hold at ZOOM_MAX."""
-    if not np.any(np.asarray(row, dtype=np.float64)) or border_taps_inside(H, W, intrinsics, family, row, 1.0):
-        return 1.0
-    if not border_taps_inside(H, W, intrinsics, family, row, ZOOM_MAX):
-        raise ValueError(f"{name}: the lens distortion leaves blank pixels even at a zoom of {ZOOM_MAX:g}; the set cannot be undistorted at its own size")
-    lo, hi = 1.0, ZOOM_MAX
-    while hi - lo > ZOOM_TOL:
-        mid = 0.5 * (lo + hi)
-        lo, hi = (lo, mid) if border_taps_inside(H, W, intrinsics, family, row, mid) else (mid, hi)
-    return hi
-
-
-def _f32(x):
-    return torch.tensor(float(x), dtype=torch.float32)
-
-
-def _atan_f32(r):
-    """lens_atan of csrc/capture.hip, r >= 0 fp32: reduction by 1 / r and (t - 1) / (t + 1), Taylor series to z^17 by Horner, every step one
-    fp32 rounding."""
-    inv = r > 1
-    t = torch.where(inv, torch.ones_like(r) / r, r)
-    red = t > _f32(0.41421356237309503)
-    z = torch.where(red, (t - 1) / (t + 1), t)
-    z2 = z * z
-    p = _f32(1 / 17).expand_as(z)
-    for n, sign in ((15, -1), (13, 1), (11, -1), (9, 1), (7, -1), (5, 1), (3, -1)):
-        p = p * z2 + _f32(1 / n) if sign > 0 else p * z2 - _f32(1 / n)
-    p = p * z2 + 1
-    a = p * z
-    a = torch.where(red, a + _f32(0.78539816339744831), a)
-    return torch.where(inv, _f32(1.5707963267948966) - a, a)
-
-
-def lens_distort_f32(family, k, x, y):
-    """The device function lens_distort of csrc/capture.hip as a torch statement: fp32 CPU tensors x, y; k [...,8] fp32, broadcast against
-    them along its leading dimensions.  Each operation below is one fp32 rounding in the kernel's order."""
-    k0, k1, k2, k3 = k[..., 0], k[..., 1], k[..., 2], k[..., 3]
-    xx, yy = x * x, y * y
-    r2 = xx + yy
-    if family == LENS_FISHEYE:
-        r = r2.double().sqrt().float()                  # the correctly rounded fp32 root (see Capture.view)
-        th = _atan_f32(r)
-        t2 = th * th
-        t4 = t2 * t2
-        t6, t8 = t4 * t2, t4 * t4
-        thd = th * (1 + (((k0 * t2 + k1 * t4) + k2 * t6) + k3 * t8))
-        scale = torch.where(r < _f32(1e-8), _f32(1.0), thd / r)
-        return x * scale, y * scale
-    r4, xy = r2 * r2, x * y
-    radial = k0 * r2 + k1 * r4
-    a, b = k2 * xy, k3 * xy
-    return (x + ((x * radial + (a + a)) + k3 * (r2 + (xx + xx))),
-            y + ((y * radial + (b + b)) + k2 * (r2 + (yy + yy))))
-
-
-def undistort_source_f32(rows, cols, src_k, out_k, lens, family):
-    """(u, v) fp32: where in the source image (continuous coordinates, pixel c covers [c, c + 1)) the centre of output pixel (rows, cols)
-    comes from -- the first half of the undistort kernel.  rows, cols int tensors [..., P]; src_k, out_k [..., 1, 4] and lens [..., 1, 8]
-    fp32 (or plain [4] / [8] rows)."""
-    i, j = cols.float() + 0.5, rows.float() + 0.5
-    x, y = (i - out_k[..., 2]) / out_k[..., 0], (j - out_k[..., 3]) / out_k[..., 1]
-    xd, yd = lens_distort_f32(family, lens, x, y)
-    return src_k[..., 0] * xd + src_k[..., 2], src_k[..., 1] * yd + src_k[..., 3]
-
-
-def _lens_tables(V, src_intrinsics, out_intrinsics, lens):
-    """The three parameter sets as fp32 CPU tensors [R,4], [R,4], [R,8] with R = V when any of them has a row per view, else 1."""
-    t = [torch.as_tensor(np.asarray(a.detach().cpu() if torch.is_tensor(a) else a, dtype=np.float64)).to(torch.float32) for a in (src_intrinsics, out_intrinsics, lens)]
-    for a, n, what in zip(t, (4, 4, 8), ("src_intrinsics", "out_intrinsics", "lens")):
-        if tuple(a.shape) not in ((n,), (V, n)):
-            raise ValueError(f"{what} must be [{n}] or [{V},{n}], not {tuple(a.shape)}")
-    per_view = any(a.dim() == 2 for a in t)
-    R = V if per_view else 1
-    return [(a if a.dim() == 2 else a.unsqueeze(0).expand(R, -1)).contiguous() for a in t], per_view
-
-
-def _undistort(src, H, W, src_intrinsics, out_intrinsics, lens, family, depth, out=None):
-    V = src.shape[0]
-    want = torch.float32 if depth else torch.int32
-    if src.dim() != 2 or src.shape[1] != H * W or src.dtype != want:
-        raise ValueError(f"the source must be {'fp32' if depth else 'int32 (pack_rgba8)'} [V, H*W] = [V, {H * W}]")
-    if family not in (LENS_BROWN, LENS_FISHEYE):
-        raise ValueError(f"unknown lens family {family}")
-    (S, O, K), per_view = _lens_tables(V, src_intrinsics, out_intrinsics, lens)
-    if src.is_cuda:
-        from . import _lib as L
-        src = src.contiguous()
-        if out is None:
-            out = torch.empty_like(src)
-        S, O, K = S.to(src.device), O.to(src.device), K.to(src.device)
-        desc = L.Undistort(src=L.ptr(src), dst=L.ptr(out), V=V, H=int(H), W=int(W), model=int(family), depth=int(bool(depth)), per_view=int(per_view),
-                           src_intrinsics=L.ptr(S), out_intrinsics=L.ptr(O), lens=L.ptr(K))
-        L.call("n2m_capture_undistort", ctypes.addressof(desc), L.stream())
-        return out
-    jj, ii = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
-    u, v = undistort_source_f32(jj.reshape(-1), ii.reshape(-1), S.unsqueeze(1), O.unsqueeze(1), K.unsqueeze(1), family)
-    u, v = u.expand(V, H * W), v.expand(V, H * W)
-    vv = torch.arange(V).unsqueeze(1)
-    if depth:
-        ix, iy = u.floor().clamp(0, W - 1).long(), v.floor().clamp(0, H - 1).long()
-        val = src[vv, iy * W + ix]
-    else:
-        sx, sy = u - 0.5, v - 0.5
-        fx0, fy0 = sx.floor(), sy.floor()
-        tx, ty = (sx - fx0).unsqueeze(-1), (sy - fy0).unsqueeze(-1)
-        ix, iy = fx0.clamp(-1, W).long(), fy0.clamp(-1, H).long()
-        x0, x1, y0, y1 = ix.clamp(min=0, max=W - 1), (ix + 1).clamp(max=W - 1), iy.clamp(min=0, max=H - 1), (iy + 1).clamp(max=H - 1)
-        by = src.contiguous().view(torch.uint8).view(V, H * W, 4)
-        a, b, c, e = (by[vv, y * W + x].float() for y, x in ((y0, x0), (y0, x1), (y1, x0), (y1, x1)))
-        top, bot = a + (b - a) * tx, c + (e - c) * tx
-        q = ((top + (bot - top) * ty) + 0.5).floor().clamp(0, 255).to(torch.uint8)
-        val = q.contiguous().view(V, H * W * 4).view(torch.int32).view(V, H * W)
-    if out is not None:
-        out.copy_(val)
-        return out
-    return val
-
-
-def undistort_bank(bank, H, W, src_intrinsics, out_intrinsics, lens, family, out=None):
-    """Packed words [V,H*W] of photographs taken through a lens -> the same views through the pinhole camera `out_intrinsics`, out of place:
-    per output pixel centre the forward lens model (family, lens row) and the source camera give the sample point, four-tap bilinear per
-    8-bit channel, floor(val + 0.5) clamped to [0, 255].  src_intrinsics / out_intrinsics (fx, fy, cx, cy) and lens [8] are single rows,
-    or [V,4] / [V,8] with a row per view (any of them a table: all are taken per view).  On the GPU one kernel (n2m_capture_undistort);
-    below it the torch statement of the same fp32 arithmetic, taken on the CPU: bit for bit."""
-    return _undistort(bank, H, W, src_intrinsics, out_intrinsics, lens, family, False, out)
-
-
-def undistort_depth(planes, H, W, src_intrinsics, out_intrinsics, lens, family, out=None):
-    """fp32 planes [V,H*W] (rows of a dense-depth bank) through the same map, taking the NEAREST source texel -- the one that contains the
-    sample point -- so that no output depth mixes two surfaces: every output value is a value of its source plane.  The zoom changes no
-    value: a depth is measured along the ray, and the pose is unchanged.  The depth mode of n2m_capture_undistort / its torch statement."""
-    return _undistort(planes, H, W, src_intrinsics, out_intrinsics, lens, family, True, out)
+def _dense_depth_bank(depth_files, tab, cam, sel, device):
+    """The depth maps of the split's views (tab, sel: their keypoint tables and indices among the kept images), each resized, calibrated
+    to its keypoints and, with a lens, resampled: the bank [V,H*W] fp32 on `device`, (scale, bias) [V,2] float64, and per view what was fitted."""
+    H, W = cam.H, cam.W
+    bank = torch.empty(len(sel), H * W, dtype=torch.float32, device=device)
+    scale_bias, samples = np.zeros((len(sel), 2), dtype=np.float64), []
+    for n, i in enumerate(sel):
+        m = np.load(depth_files[n])
+        if m.ndim != 2 or m.size == 0 or not np.issubdtype(m.dtype, np.number):
+            raise ValueError(f"{depth_files[n]} holds an array of shape {m.shape}, not a 2-D depth map")
+        m = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32))
+        rc = torch.from_numpy(tab[n][0]).long()
+        if cam.family is not None:
+            # the undistorted plane at the (undistorted) keypoints = the resized map at the texel the kernel takes for them
+            row_f32 = [torch.from_numpy(a[i].astype(np.float32)) for a in (cam.src_rows, cam.out_rows, cam.lens_rows)]
+            u, v = undistort_source_f32(rc[:, 0], rc[:, 1], *row_f32, cam.family)
+            rc = torch.stack([v.floor().clamp(0, H - 1).long(), u.floor().clamp(0, W - 1).long()], -1)
+        x = resize_linear_at(m, H, W, rc[:, 0], rc[:, 1]).double().numpy()        # the resized map at the keypoints, on the host
+        try:
+            sb = fit_scale_bias(x, tab[n][3], tab[n][4])
+        except ValueError as e:
+            raise ValueError(f"{depth_files[n]}: {e}") from None
+        scale_bias[n] = sb
+        samples.append(np.stack([x, tab[n][3], tab[n][4]], -1))
+        if cam.family is None:
+            dense_depth_fill(m.to(device), H, W, sb[0], sb[1], out=bank[n])      # one view at a time: no full-size host copy
+        else:       # resized and calibrated as the lens saw it, then resampled: a nearest gather moves values, the affine map commutes with it
+            plane = dense_depth_fill(m.to(device), H, W, sb[0], sb[1]).view(1, H * W)
+            undistort_depth(plane, H, W, cam.src_rows[i], cam.out_rows[i], cam.lens_rows[i], cam.family, out=bank[n:n + 1])
+    return bank, scale_bias, samples
 
 
 class Capture:
@@ -835,7 +592,7 @@ class Capture:
         self.H, self.W = int(H), int(W)
         poses_cpu = torch.as_tensor(poses).detach().float().cpu().contiguous()
         V = poses_cpu.shape[0] if poses_cpu.dim() == 3 else 0
-        intr = (intrinsics.detach().double().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics, dtype=np.float64))
+        intr = as_f64(intrinsics)
         if intr.shape == (4,):
             table = np.tile(intr, (V, 1)) if per_view else None
         elif intr.shape == (V, 4):
@@ -863,11 +620,8 @@ class Capture:
         self.cam_near_far = None if cam_near_far is None else torch.as_tensor(cam_near_far).float().to(device).contiguous()
         if self.per_view_intrinsics:
             self.intrinsics = torch.from_numpy(self.intrinsics_host.astype(np.float32)).to(device).contiguous()
-            self.mvps = torch.stack([proj_matrix(self.H, self.W, *(float(x) for x in self.intrinsics_host[v])) @ torch.inverse(p)
-                                     for v, p in enumerate(poses_cpu)]).to(device)
-            return
-        proj = proj_matrix(self.H, self.W, *self.intrinsics)
-        self.mvps = torch.stack([proj @ torch.inverse(p) for p in poses_cpu]).to(device)      # per pose on the host, like synthetic.mvp_matrix
+        self.mvps = torch.stack([proj_matrix(self.H, self.W, *self.intrinsics_of(v)) @ torch.inverse(p)      # per pose on the host, like
+                                 for v, p in enumerate(poses_cpu)]).to(device)                                # synthetic.mvp_matrix
 
     def intrinsics_of(self, v):
         """(fx, fy, cx, cy) of view v as Python floats, from the host copy: no device read."""
@@ -887,10 +641,7 @@ class Capture:
             raise ValueError("downscale must be a positive integer")
         if k > 1:
             bank = box_downscale(bank, H, W, k)
-            if np.ndim(intrinsics) == 2:
-                intrinsics = (intrinsics.detach().double().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics, dtype=np.float64)) / k
-            else:
-                intrinsics = tuple(float(x) / k for x in intrinsics)
+            intrinsics = as_f64(intrinsics) / k
             H, W = H // k, W // k
         return cls(poses, bank, H, W, intrinsics, has_alpha=has_alpha, linear=linear, cam_near_far=cam_near_far, device=device, per_view=per_view)
 
@@ -899,7 +650,6 @@ class Capture:
         """transforms_{split}.json (else transforms.json) by the rules of nerf/provider.py:150-263: H, W from h / w or the first image, focal
         from fl_x / fl_y else camera_angle_x / camera_angle_y, cx, cy default to W / 2, H / 2, `.png` appended to a file name without an
         extension, missing files skipped, poses through nerf_matrix_to_ngp.  Images are read with PIL."""
-        from PIL import Image
         name = os.path.join(path, f"transforms_{split}.json")
         if not os.path.exists(name):
             name = os.path.join(path, "transforms.json")
@@ -914,10 +664,7 @@ class Capture:
                 fp += ".png"
             if not os.path.exists(fp):
                 continue
-            with Image.open(fp) as im:
-                if im.mode not in ("RGB", "RGBA"):
-                    im = im.convert("RGBA" if "A" in im.getbands() or "transparency" in im.info else "RGB")
-                images.append(np.asarray(im, dtype=np.uint8))
+            images.append(_read_image(fp))
             poses.append(nerf_matrix_to_ngp(fr["transform_matrix"], scale, offset))
         if not images:
             raise FileNotFoundError(f"{name} lists no image that exists")
@@ -969,140 +716,22 @@ class Capture:
         undistorted keypoints.  A set whose kept cameras all have zero coefficients skips the pass: bit for bit undistort=False."""
         if split not in ("train", "val", "trainval"):
             raise ValueError(f"split must be train, val or trainval, not {split!r}")
-        root = next((os.path.join(path, *c) for c in COLMAP_DIRS if os.path.exists(os.path.join(path, *c))), None)
-        if root is None:
-            raise ValueError(f"no COLMAP model under {path} (colmap_sparse/0, sparse/0, colmap)")
-        cams = read_colmap_cameras(os.path.join(root, "cameras.bin"))
-        ims = read_colmap_images(os.path.join(root, "images.bin"))
-        pids, pts3d, perr = read_colmap_points(os.path.join(root, "points3D.bin"))
-        if len(pids) == 0:
-            raise ValueError(f"{root}: the reconstruction has no 3D points")
         ds = downscale
-        folder = os.path.join(path, f"images_{ds}")
-        own_folder = os.path.exists(folder)
-        if not own_folder:
-            folder = os.path.join(path, "images")
-        keys = [k for k in sorted(ims) if os.path.exists(os.path.join(folder, os.path.basename(ims[k]["name"])))]
-        if not keys:
-            raise FileNotFoundError(f"{root}/images.bin lists no image that exists under {folder}")
-        # one camera model per set
-        used = sorted({ims[k]["camera_id"] for k in keys})
-        intr, lens = [], []
-        for c in used:
-            cam = cams[c]
-            if undistort:
-                f4, fam, row = lens_row(cam["model"], cam["params"])
-                lens.append((fam,) + tuple(row))
-            elif cam["model"] in ("SIMPLE_PINHOLE", "SIMPLE_RADIAL"):
-                f4 = (cam["params"][0], cam["params"][0], cam["params"][1], cam["params"][2])
-            elif cam["model"] in ("PINHOLE", "OPENCV"):
-                f4 = tuple(cam["params"][:4])
-            else:
-                raise ValueError(f"unsupported COLMAP camera model: {cam['model']}")
-            intr.append((cam["height"], cam["width"]) + tuple(float(x) for x in f4))
-        # the lens of the set: rows with a coefficient share one family; none has one -> no pass at all
-        family = None
-        if any(any(l[1:]) for l in lens):
-            fams = {l[0] for l in lens if any(l[1:])}
-            if len(fams) != 1:
-                raise ValueError("the kept images mix fisheye and polynomial lens models; a set is undistorted with one model family")
-            family = fams.pop()
-            intr = [i + l[1:] for i, l in zip(intr, lens)]             # cameras that differ in their lens alone are different cameras
-        table = None
-        if any(i != intr[0] for i in intr[1:]):
-            if not per_view_intrinsics:
-                raise ValueError(f"the kept images use {len(used)} cameras with different parameters; a Capture holds one camera model per set "
-                                 "unless it is loaded with per_view_intrinsics=True (tools/train_capture.py --per_view_intrinsics)")
-            if any(i[:2] != intr[0][:2] for i in intr[1:]):
-                raise ValueError(f"the kept images use cameras of differing image sizes ({sorted({i[:2] for i in intr})} as height x width); "
-                                 "per-view intrinsics still need one image size per set")
-            by_id = dict(zip(used, intr))
-            table = np.array([by_id[ims[k]["camera_id"]][2:6] for k in keys], dtype=np.float64) / ds
-        h0, w0 = intr[0][:2]
-        H, W = int(round(h0 / ds)), int(round(w0 / ds))
-        fx, fy, cx, cy = (x / ds for x in intr[0][2:6])
-        if family is not None:
-            # per kept image: its lens row, its source intrinsics at the bank's size, and the zoom of its camera (one bisection per camera)
-            by_id = dict(zip(used, intr))
-            lens_rows = np.array([by_id[ims[k]["camera_id"]][6:] for k in keys], dtype=np.float64)
-            src_rows = np.array([by_id[ims[k]["camera_id"]][2:6] for k in keys], dtype=np.float64) / ds
-            zoom_of = {c: undistort_zoom(H, W, np.asarray(by_id[c][2:6]) / ds, family, by_id[c][6:], name=f"camera {c}") for c in used}
-            zooms = np.array([zoom_of[ims[k]["camera_id"]] for k in keys], dtype=np.float64)
-            out_rows = src_rows * np.stack([zooms, zooms, np.ones_like(zooms), np.ones_like(zooms)], -1)
-            if table is not None:
-                table = out_rows
-            fx, fy = out_rows[0, 0], out_rows[0, 1]
-        # poses: camera-to-world = inv([R|t]) = [R^T | -R^T t]
-        poses = np.tile(np.eye(4), (len(keys), 1, 1))
-        for n, k in enumerate(keys):
-            R = quat_to_rotmat(ims[k]["q"])
-            poses[n, :3, :3] = R.T
-            poses[n, :3, 3] = -R.T @ ims[k]["t"]
-        poses, pts = center_poses(poses, pts3d, enable_cam_center)
-        poses, pts = _world_flip(poses, pts)
-        if scale == -1:
-            scale = 1.0 / np.linalg.norm(poses[:, :3, 3], axis=-1).min()
-        poses[:, :3, 3] *= scale
-        pts = pts * scale
-        pts_aabb = np.concatenate([pts.min(0), pts.max(0)]).astype(np.float32)
-        # keypoints -> sparse depth, per kept image
-        mean_err = perr.mean()
-        cnf, tab, kps = [], [], []
-        for n, k in enumerate(keys):
-            xy, ids = ims[k]["xys"], ims[k]["point3D_ids"]
-            if family is not None and len(xy):
-                # distorted full-size pixels -> normalised -> ideal (host inverse) -> pixels of the zoomed camera, still at full size
-                sfx, sfy, scx, scy = src_rows[n] * ds
-                try:
-                    ux, uy = lens_undistort(family, lens_rows[n], (xy[:, 0] - scx) / sfx, (xy[:, 1] - scy) / sfy)
-                except ValueError as e:
-                    raise ValueError(f"image {ims[k]['name']}: {e}") from None
-                xy = np.stack([zooms[n] * sfx * ux + scx, zooms[n] * sfy * uy + scy], -1)
-            if keep_model:
-                found = np.searchsorted(pids, ids).clip(0, len(pids) - 1)
-                kps.append((xy, np.where((ids != -1) & (pids[found] == ids), found, -1)))       # as indices into the sorted point list
-            rowcol = np.stack([xy[:, 1], xy[:, 0]], -1)
-            m = (ids != -1) & (rowcol[:, 0] >= 0) & (rowcol[:, 0] < h0) & (rowcol[:, 1] >= 0) & (rowcol[:, 1] < w0)
-            if not m.any():
-                raise ValueError(f"image {ims[k]['name']} has no keypoint with a 3D point inside the image")
-            at = np.searchsorted(pids, ids[m])
-            if (at >= len(pids)).any() or (pids[np.minimum(at, len(pids) - 1)] != ids[m]).any():
-                raise ValueError(f"image {ims[k]['name']} refers to a 3D point that points3D.bin does not hold")
-            rc = np.round(rowcol[m] / ds).astype(np.int32)
-            rc[:, 0] = rc[:, 0].clip(0, H - 1)
-            rc[:, 1] = rc[:, 1].clip(0, W - 1)
-            P = poses[n]
-            depth = (P[:3, 3] - pts[at]) @ P[:3, 2]
-            weight = 2 * np.exp(-(perr[at] / mean_err) ** 2)
-            cnf.append([depth.min(), depth.max()])
-            tab.append((rc, depth.astype(np.float32), weight.astype(np.float32), depth, weight))
-        sel = list(range(len(keys)))
-        if split == "val":
-            sel = sel[::8]
-        elif split == "train":
-            sel = [i for i in sel if i % 8 != 0]
-        if not sel:
-            raise ValueError(f"the {split} split of {len(keys)} images is empty")
-        depth_files = [os.path.join(path, "depths", os.path.splitext(os.path.basename(ims[keys[i]]["name"]))[0] + ".npy") for i in sel]
+        cams, ims, (pids, pts3d, perr), folder, own_folder, keys = _colmap_model(path, ds)
+        cam = _colmap_cameras(cams, [ims[k]["camera_id"] for k in keys], undistort, per_view_intrinsics, ds)
+        H, W = cam.H, cam.W
+        poses, pts, scale, pts_aabb = _colmap_poses(ims, keys, pts3d, enable_cam_center, scale)
+        kps, tab, cnf = _colmap_keypoints(ims, keys, cam, ds, poses, pts, pids, perr, keep_model)
+        sel = _split(len(keys), split)
+        tab = [tab[i] for i in sel]
+        names = [os.path.basename(ims[keys[i]]["name"]) for i in sel]
+        stems = [os.path.splitext(b)[0] for b in names]
+        depth_files = [os.path.join(path, "depths", s + ".npy") for s in stems]
         if dense_depth:
             for name in depth_files:
                 if not os.path.exists(name):
                     raise FileNotFoundError(f"dense depth asked for, but there is no {name}")
-        # images (+ masks) of the split
-        mask_dir = os.path.join(path, "mask")
-        images = []
-        for i in sel:
-            base = os.path.basename(ims[keys[i]]["name"])
-            im = _read_image(os.path.join(folder, base))
-            mname = os.path.join(mask_dir, os.path.splitext(base)[0] + ".png")
-            if os.path.isdir(mask_dir) and os.path.exists(mname):
-                mk = _read_image(mname)
-                if mk.shape[:2] != im.shape[:2]:
-                    raise ValueError(f"{mname} is {mk.shape[0]} x {mk.shape[1]}, its image {im.shape[0]} x {im.shape[1]}")
-                im = np.concatenate([im[..., :3], mk[..., :1]], -1)
-            images.append(im)
-        if any(im.shape[-1] == 4 for im in images):         # a mask for some views only: the others are opaque
-            images = [im if im.shape[-1] == 4 else np.concatenate([im, np.full_like(im[..., :1], 255)], -1) for im in images]
+        images = _read_images([(os.path.join(folder, b), os.path.join(path, "mask", s + ".png")) for b, s in zip(names, stems)], require_mask=False)
         if any(im.shape != images[0].shape for im in images):
             raise ValueError("all images of a set must share one size")
         bank, has_alpha = pack_rgba8(np.stack(images))
@@ -1110,53 +739,27 @@ class Capture:
         ih, iw = images[0].shape[:2]
         if (ih, iw) != (H, W):
             k = int(ds)
-            if own_folder or k != ds or (ih, iw) != (h0, w0) or (ih // k, iw // k) != (H, W):
-                raise ValueError(f"the images are {ih} x {iw}, the cameras state {h0} x {w0} at downscale {ds}: only the full-size images "
+            if own_folder or k != ds or (ih, iw) != (cam.h0, cam.w0) or (ih // k, iw // k) != (H, W):
+                raise ValueError(f"the images are {ih} x {iw}, the cameras state {cam.h0} x {cam.w0} at downscale {ds}: only the full-size images "
                                  "with an integer downscale that divides them can be reduced here")
             bank = box_downscale(bank, ih, iw, k)
-        if family is not None:
-            one = table is None
-            lens_arg = (src_rows[0], out_rows[0], lens_rows[0]) if one else (src_rows[sel], out_rows[sel], lens_rows[sel])
-            bank = undistort_bank(bank, H, W, *lens_arg, family)
-        cap = cls(poses[sel].astype(np.float32), bank, H, W, (fx, fy, cx, cy) if table is None else table[sel], has_alpha=has_alpha, linear=linear,
-                  cam_near_far=np.asarray(cnf, dtype=np.float32)[sel], device=device)
+        if cam.family is not None:
+            rows = sel if cam.per_view else 0            # one row for the set, or a row per view
+            bank = undistort_bank(bank, H, W, cam.src_rows[rows], cam.out_rows[rows], cam.lens_rows[rows], cam.family)
+        cap = cls(poses[sel].astype(np.float32), bank, H, W, cam.intrinsics[sel] if cam.per_view else cam.intrinsics, has_alpha=has_alpha,
+                  linear=linear, cam_near_far=cnf[sel], device=device)
         cap.pts_aabb = torch.from_numpy(pts_aabb)
         cap.scale = float(scale)
         if undistort:
-            cap.undistort_zoom = 1.0 if family is None else float(zooms[0]) if table is None else zooms[sel]
+            cap.undistort_zoom = 1.0 if cam.family is None else cam.zooms[sel] if cam.per_view else float(cam.zooms[0])
         if keep_model:
-            cap.colmap = dict(points=pts, errors=perr, keypoints=[kps[i] for i in sel], names=[os.path.basename(ims[keys[i]]["name"]) for i in sel])
+            cap.colmap = dict(points=pts, errors=perr, keypoints=[kps[i] for i in sel], names=names)
         if sparse_depth:
-            off = np.concatenate([[0], np.cumsum([len(tab[i][1]) for i in sel])])
-            cap.sparse_depth = SparseDepth(off, np.concatenate([tab[i][0] for i in sel]), np.concatenate([tab[i][1] for i in sel]),
-                                           np.concatenate([tab[i][2] for i in sel]), device=cap.device)
+            off = np.concatenate([[0], np.cumsum([len(t[1]) for t in tab])])
+            cap.sparse_depth = SparseDepth(off, np.concatenate([t[0] for t in tab]), np.concatenate([t[1] for t in tab]),
+                                           np.concatenate([t[2] for t in tab]), device=cap.device)
         if dense_depth:
-            cap.dense_depth = torch.empty(len(sel), H * W, dtype=torch.float32, device=cap.device)
-            cap.dense_depth_scale_bias = np.zeros((len(sel), 2), dtype=np.float64)
-            samples = []
-            for n, i in enumerate(sel):
-                m = np.load(depth_files[n])
-                if m.ndim != 2 or m.size == 0 or not np.issubdtype(m.dtype, np.number):
-                    raise ValueError(f"{depth_files[n]} holds an array of shape {m.shape}, not a 2-D depth map")
-                m = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32))
-                rc = torch.from_numpy(tab[i][0]).long()
-                if family is not None:
-                    # the undistorted plane at the (undistorted) keypoints = the resized map at the texel the kernel takes for them
-                    row_f32 = [torch.from_numpy(a[i].astype(np.float32)) for a in (src_rows, out_rows, lens_rows)]
-                    u, v = undistort_source_f32(rc[:, 0], rc[:, 1], *row_f32, family)
-                    rc = torch.stack([v.floor().clamp(0, H - 1).long(), u.floor().clamp(0, W - 1).long()], -1)
-                x = resize_linear_at(m, H, W, rc[:, 0], rc[:, 1]).double().numpy()        # the resized map at the keypoints, on the host
-                try:
-                    sb = fit_scale_bias(x, tab[i][3], tab[i][4])
-                except ValueError as e:
-                    raise ValueError(f"{depth_files[n]}: {e}") from None
-                cap.dense_depth_scale_bias[n] = sb
-                samples.append(np.stack([x, tab[i][3], tab[i][4]], -1))
-                if family is None:
-                    dense_depth_fill(m.to(cap.device), H, W, sb[0], sb[1], out=cap.dense_depth[n])      # one view at a time: no full-size host copy
-                else:       # resized and calibrated as the lens saw it, then resampled: a nearest gather moves values, the affine map commutes with it
-                    plane = dense_depth_fill(m.to(cap.device), H, W, sb[0], sb[1]).view(1, H * W)
-                    undistort_depth(plane, H, W, src_rows[i], out_rows[i], lens_rows[i], family, out=cap.dense_depth[n:n + 1])
+            cap.dense_depth, cap.dense_depth_scale_bias, samples = _dense_depth_bank(depth_files, tab, cam, sel, cap.device)
             if keep_model:
                 cap.dense_depth_samples = samples
         return cap
@@ -1205,16 +808,7 @@ class Capture:
         sel = sel[1:] if split == "train" else sel[:1] if split == "val" else sel
         if not sel:
             raise ValueError(f"the {split} split of {len(names)} images is empty")
-        images = []
-        for i in sel:
-            im = _read_image(os.path.join(path, "image", names[i]))
-            mname = os.path.join(path, "mask", names[i])
-            if not os.path.exists(mname):
-                raise FileNotFoundError(f"image/{names[i]} has no mask: {mname} is missing")
-            mk = _read_image(mname)
-            if mk.shape[:2] != im.shape[:2]:
-                raise ValueError(f"{mname} is {mk.shape[0]} x {mk.shape[1]}, its image {im.shape[0]} x {im.shape[1]}")
-            images.append(np.concatenate([im[..., :3], mk[..., :1]], -1))
+        images = _read_images([(os.path.join(path, "image", names[i]), os.path.join(path, "mask", names[i])) for i in sel], require_mask=True)
         if any(im.shape != images[0].shape for im in images):
             raise ValueError("all images of a set must share one size (per-view image sizes are not supported)")
         cap = cls.from_arrays(poses[sel], np.stack(images), np.asarray(rows, dtype=np.float64)[sel], linear=linear, downscale=k, device=device)
@@ -1232,14 +826,10 @@ class Capture:
         if intrinsics is None:
             intrinsics = (synthetic.LEGO_FOCAL, synthetic.LEGO_FOCAL, W / 2, H / 2)
         V = poses.shape[0]
-        if np.ndim(intrinsics) == 2:
-            intr = intrinsics.detach().double().cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics, dtype=np.float64)
-            if intr.shape != (V, 4):
-                raise ValueError(f"per-view intrinsics must be [{V},4], not {intr.shape}")
-            rows = [tuple(float(x) for x in r) for r in intr]
-        else:
-            intr = tuple(float(x) for x in intrinsics)
-            rows = [intr] * V
+        intr = as_f64(intrinsics)
+        if intr.ndim == 2 and intr.shape != (V, 4):
+            raise ValueError(f"per-view intrinsics must be [{V},4], not {intr.shape}")
+        rows = [intrinsics_row(intr, v) for v in range(V)]
         pd, bx = poses.to(dev), synthetic.boxes(dev, scene)
         images = torch.empty(V, H * W, 4 if alpha else 3, dtype=torch.uint8, device=dev)
         pix = torch.arange(H * W, device=dev)
@@ -1374,12 +964,7 @@ class Capture:
         # back to COLMAP's frame: undo the scale, then the convention change (its own inverse on the world side)
         poses = self.poses.double().cpu().numpy().copy()
         poses[:, :3, 3] /= scale
-        poses = poses[:, [1, 0, 2, 3], :]              # inverse of _world_flip: the world side is its own inverse, then the camera axes
-        poses[:, 2] *= -1
-        poses[:, :3, 1:3] *= -1
-        pw = points / scale
-        pw = pw[:, [1, 0, 2]].copy()
-        pw[:, 2] *= -1
+        poses, pw = _world_flip(poses, points / scale)         # its own inverse: sign changes and a swap, which commute
         if keypoints is None:
             keypoints = []
             for v in range(V):
@@ -1396,44 +981,25 @@ class Capture:
         root = os.path.join(path, *folder.split("/"))
         os.makedirs(root, exist_ok=True)
         os.makedirs(os.path.join(path, "images"), exist_ok=True)
-        with open(os.path.join(root, "cameras.bin"), "wb") as f:
-            f.write(struct.pack("<Q", len(cam_rows)))
-            for n, params in enumerate(cam_params):
-                f.write(struct.pack("<iiQQ", n + 1, mid, self.W, self.H))
-                f.write(np.asarray(params, dtype="<f8").tobytes())
+        write_colmap_cameras(os.path.join(root, "cameras.bin"), mid, self.W, self.H, cam_params)
+        qt, kp_ids = [], []
+        for v in range(V):
+            Rt = poses[v, :3, :3].T                                  # world-to-camera rotation
+            qt.append(np.concatenate([rotmat_to_quat(Rt), -Rt @ poses[v, :3, 3]]))
+            xy, idx = keypoints[v]
+            xy, idx = np.asarray(xy, dtype=np.float64).reshape(-1, 2), np.asarray(idx, dtype=np.int64).reshape(-1)
+            kp_ids.append((xy, np.where(idx >= 0, ids[np.clip(idx, 0, M - 1)], -1)))
+        tracks = write_colmap_images(os.path.join(root, "images.bin"), qt, [cam_id[r] for r in rows], names, kp_ids)
         by = self.bank_bytes().cpu().numpy()
-        tracks = {}
-        with open(os.path.join(root, "images.bin"), "wb") as f:
-            f.write(struct.pack("<Q", V))
-            for v in range(V):
-                Rt = poses[v, :3, :3].T                                  # world-to-camera rotation
-                f.write(struct.pack("<i", v + 1))
-                f.write(np.concatenate([rotmat_to_quat(Rt), -Rt @ poses[v, :3, 3]]).astype("<f8").tobytes())
-                f.write(struct.pack("<i", cam_id[rows[v]]))
-                f.write(names[v].encode() + b"\0")
-                xy, idx = keypoints[v]
-                xy, idx = np.asarray(xy, dtype=np.float64).reshape(-1, 2), np.asarray(idx, dtype=np.int64).reshape(-1)
-                pid = np.where(idx >= 0, ids[np.clip(idx, 0, M - 1)], -1)
-                rec = np.empty(len(idx), dtype=np.dtype([("xy", "<f8", 2), ("id", "<i8")]))
-                rec["xy"], rec["id"] = xy, pid
-                f.write(struct.pack("<Q", len(idx)))
-                f.write(rec.tobytes())
-                for j, p in enumerate(pid):
-                    if p != -1:
-                        tracks.setdefault(int(p), []).append((v + 1, j))
-                Image.fromarray(by[v] if self.has_alpha else np.ascontiguousarray(by[v, :, :, :3])).save(os.path.join(path, "images", names[v]))
+        for v in range(V):
+            Image.fromarray(by[v] if self.has_alpha else np.ascontiguousarray(by[v, :, :, :3])).save(os.path.join(path, "images", names[v]))
         if depths is not None:
             if len(depths) != V or any(np.ndim(d) != 2 for d in depths):
                 raise ValueError(f"depths must be one 2-D array per view ({V} views)")
             os.makedirs(os.path.join(path, "depths"), exist_ok=True)
             for v in range(V):
                 np.save(os.path.join(path, "depths", os.path.splitext(names[v])[0] + ".npy"), np.asarray(depths[v]))
-        with open(os.path.join(root, "points3D.bin"), "wb") as f:
-            f.write(struct.pack("<Q", M))
-            for m in range(M):
-                tr = tracks.get(int(ids[m]), [])
-                f.write(struct.pack("<QdddBBBdQ", int(ids[m]), *pw[m], 128, 128, 128, float(errors[m]), len(tr)))
-                f.write(np.asarray(tr, dtype="<i4").tobytes())
+        write_colmap_points(os.path.join(root, "points3D.bin"), ids, pw, errors, tracks)
 
     def save_dtu(self, path, scale=1.0, offset=(0, 0, 0)):
         """Writes the set in the DTU layout (cameras_sphere.npz with world_mat_i = K_i [R_i | -R_i C_i] padded to 4 x 4 and an identity
