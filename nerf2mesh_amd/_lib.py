@@ -6,6 +6,7 @@ PyTorch fallback anywhere in the package.
 import ctypes
 import os
 import threading
+import time
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("N2M_HIP_LIB") or os.path.join(_HERE, "lib", "libn2m_hip.so")   # override: A/B builds of the same ABI
@@ -354,6 +355,35 @@ def call(name, *args):
     rc = getattr(L, name)(*args)
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {L.n2m_last_error().decode()}")
+
+
+class thread_locals:
+    """Context: sticky thread-local settings of the library, each stated as (setter, *args) -- a false entry is skipped, so a condition can
+    stand in its place.  Set, in the order given, right in front of the calls they are meant for and cleared behind them in the same order
+    (the setter with NULL for every argument) whatever happens in between: an exception must not leave a stale pointer for the next call of
+    this thread."""
+    __slots__ = ("settings",)
+
+    def __init__(self, *settings):
+        self.settings = [s for s in settings if s]
+
+    def __enter__(self):
+        for s in self.settings:
+            call(*s)
+
+    def __exit__(self, *exc):
+        for s in self.settings:
+            call(s[0], *[None] * (len(s) - 1))
+
+
+def wait_polled(event, limit=5e-3):
+    """Wait for a torch event by polling, blocking only after `limit` seconds: hipEventSynchronize parks the thread, and waking it costs tens
+    of microseconds the GPU then idles."""
+    t0 = time.perf_counter()
+    while not event.query():
+        if time.perf_counter() - t0 > limit:
+            event.synchronize()
+            break
 
 
 _BWD_CFG = threading.local()
