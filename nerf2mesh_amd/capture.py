@@ -328,7 +328,21 @@ class DepthSchedule:
 
     def __init__(self, n_views, seed=0):
         import random
+        self.seed = seed
         self.rng, self.n, self.order, self.log = random.Random(seed), int(n_views), [], []
+
+    def state_dict(self, position=None):
+        """The schedule's position: how many decisions it has handed out (`position`: an earlier one -- a driver that prepares batches ahead
+        saves the position in front of the oldest batch it has not run yet)."""
+        return {"position": len(self.log) if position is None else int(position), "n_views": self.n}
+
+    def load_state_dict(self, sd):
+        """Walks a schedule of the same seed to the saved position: the sequence is a function of the seed alone."""
+        if int(sd["n_views"]) != self.n:
+            raise ValueError(f"depth_schedule.n_views: the checkpoint has {int(sd['n_views'])} views, the capture {self.n}")
+        self.__init__(self.n, self.seed)
+        for _ in range(int(sd["position"])):
+            self.next()
 
     def next(self):
         view = None

@@ -799,6 +799,46 @@ class Stage0Engine:
             self.sync_parameters()          # each rank has advanced its own rows of the fp32 tables only (a collective, at a symmetric step)
         self.ema.update()
 
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """Everything the next train_step() depends on, under the reference's checkpoint keys (nerf/utils.py:1345-1365) plus "n2m": each layer
+        names the state it owns -- the model, optimizer and EMA theirs, `batches` the pipeline's, this class its counters.  A fresh engine
+        built with the same arguments continues bit for bit after load_state_dict() (tests/test_checkpoint_engine_gpu.py).  COLLECTIVE when
+        the optimizer is sharded (optimizer.state_dict() gathers the moments)."""
+        from . import checkpoint
+        self.sync_parameters()
+        sd = checkpoint.stage0_state(self)
+        sd["n2m"].update(driver="Stage0Engine", batches=self.batches.state_dict())
+        if hasattr(self, "last_fold_left"):
+            sd["n2m"]["last_fold_left"] = int(self.last_fold_left)
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, model_only=False):
+        """model_only: the model, the averaged weights and mean_density alone (the reference's rule, nerf/utils.py:1446-1447)."""
+        from . import checkpoint
+        if self.world > 1:
+            raise NotImplementedError("loading a checkpoint into a multi-rank engine (the packed rows and shards of every rank would have to follow)")
+        torch.cuda.synchronize(self.device)
+        checkpoint.load_stage0_state(self, sd, model_only)
+        if model_only:
+            return
+        n2m = sd.get("n2m", {})
+        self.batches.load_state_dict(checkpoint.batch_state(sd))
+        self.adam.reset()
+        # gradient buffers are all-zero between steps (the optimizer pass clears them); nothing of an interrupted step may survive
+        self.dw.zero_()
+        if self.dcodes is not None:
+            self.dcodes.zero_()
+        if self._sdf is not None:
+            self._sdf["d_var"].zero_()
+            self._sdf["fold_cnt"].zero_()
+        self._corners_of = None
+        if "last_fold_left" in n2m:
+            self.last_fold_left = int(n2m["last_fold_left"])
+        elif hasattr(self, "last_fold_left"):
+            del self.last_fold_left
+
     def averaged_parameters(self):
         """Context: the model carries the EMA weights (store / copy_to ... restore, nerf/utils.py:1250-1252,1340-1341); no-op without EMA."""
         import contextlib

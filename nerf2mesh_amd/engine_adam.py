@@ -70,6 +70,15 @@ class AdamPass:
         self._synced = (-1, False, False)
         self._adam_peer = None
 
+    def reset(self):
+        """Behind a loaded checkpoint: the optimizer's moment tensors were replaced (FusedAdamAMP.state_epoch already keys the descriptors on
+        that) -- drop every cached descriptor anyway, the lookup-overlap event of a pass that no longer counts, and the fused pass's other
+        buffer set, which holds the values of a step before the load."""
+        self.wait_gather()
+        self._desc, self.packed, self.fine_ready, self._synced = {}, None, None, (-1, False, False)
+        if self.eng.fuse_adam is not None:
+            self.eng.fuse_adam.update(alt=None, desc={})
+
     # ------------------------------------------------------------------------------------------------ descriptors
     def _tables(self, pk, g1, g2, row0=0, rows=None, whole_grads=False):
         """Entries of the two tables, `rows` rows from `row0` (None: all).  whole_grads: g1 / g2 are the full gradient buffers, read from

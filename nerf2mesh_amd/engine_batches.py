@@ -39,6 +39,7 @@ class _RayBufs:
         self.args = None
         self.bits = None             # the occupancy bit field the batch was marched through (keeps its memory alive for `args`)
         self.refreshed = False
+        self.pre = None              # what the pipeline held in front of this batch's draw (BatchPipeline.state_dict)
 
 
 class BatchPipeline:
@@ -67,6 +68,7 @@ class BatchPipeline:
         self._last = None                     # the newest prepared batch
         self._queue = []                      # prepared batches, oldest first (steady state: the next one and the one after)
         self._prepared = 0                    # index (1-based) of the newest prepared batch
+        self._refreshed = 0                   # index of the newest batch whose occupancy refresh has run (a loaded state may be behind its refresh)
 
     def go_ahead(self, event):
         """The step's marker: the side stream may start the next batch behind `event` (the last kernel that reads the oldest buffer set)."""
@@ -191,13 +193,16 @@ class BatchPipeline:
                 if opt.adaptive_num_rays and M > 0 and prev.depth_view is None:      # (a depth batch does not steer the ray count)
                     eng.num_rays = max(1, int(round((opt.num_points / M) * prev.N)))
             N = int(eng.num_rays)
+            # (what a checkpoint taken while this batch waits in the queue needs: the state in front of its draws, as plain host values)
+            pre = (self.gen.get_offset(), N, eng.last_num_points, len(eng.depth_schedule.log) if eng.depth_schedule is not None else None)
             view = eng.depth_schedule.next() if eng.depth_schedule is not None else None
             if view is not None:
                 N = eng.capture.sparse_depth.counts[view]
             defer = False
             if need_refresh or not eng.overlap or self._marker is None:
-                if need_refresh:
+                if need_refresh and self._refreshed < j:
                     eng._refresh()
+                    self._refreshed = j
                 b = self.prepare(N, view)
                 if need_refresh and eng.overlap and self._marker is not None:
                     # the batch behind this one needs THIS batch's count, which the host can only wait for -- and the running step cannot be
@@ -216,11 +221,45 @@ class BatchPipeline:
                 main = torch.cuda.current_stream(self.device)
                 b.u.record_stream(main)
             b.index = j
+            b.pre = pre
             self._prepared = j
             self._last = b
             self._queue.append(b)
             if defer:
                 break
+
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """The pipeline at a step boundary, as the NEXT batch's preparation met it: the generator in front of that batch's draw, the ray
+        count and sample count it saw, the depth schedule's position, and whether its occupancy refresh has run.  The prepared batches
+        themselves are not saved: loading prepares them again from the same draws."""
+        eng = self.eng
+        nxt = self._queue[0].pre if self._queue else None
+        gen = self.gen.get_state()
+        if nxt is not None:
+            g = torch.Generator(device=self.device)
+            g.set_state(gen)
+            g.set_offset(nxt[0])
+            gen = g.get_state()
+        _, num_rays, last, pos = nxt if nxt is not None else (None, int(eng.num_rays), eng.last_num_points,
+                                                              len(eng.depth_schedule.log) if eng.depth_schedule is not None else None)
+        step = self._queue[0].index - 1 if self._queue else self._prepared
+        return {"gen": gen, "num_rays": int(num_rays), "last_num_points": int(last), "prepared": int(step),
+                "refreshed": int(self._refreshed) if self._refreshed > step else 0,
+                "depth_schedule": None if eng.depth_schedule is None else eng.depth_schedule.state_dict(pos)}
+
+    def load_state_dict(self, sd):
+        """Drops every prepared batch; the next take() prepares batch `prepared` + 1 from the loaded generator."""
+        eng = self.eng
+        torch.cuda.current_stream(self.device).wait_stream(self.side)      # (nothing of the dropped batches is still being written)
+        self._queue, self._last, self._marker, self._post_refresh, self._mid_fill = [], None, None, None, False
+        self._prepared, self._refreshed = int(sd["prepared"]), int(sd.get("refreshed", 0))
+        self.gen.set_state(sd["gen"].cpu())
+        eng.num_rays, eng.last_num_points = int(sd["num_rays"]), int(sd["last_num_points"])
+        if (eng.depth_schedule is None) != (sd.get("depth_schedule") is None):
+            raise ValueError("depth_schedule: the checkpoint and this driver disagree on enable_sparse_depth")
+        if eng.depth_schedule is not None:
+            eng.depth_schedule.load_state_dict(sd["depth_schedule"])
 
     def mid_step_fill(self):
         """Behind the step's first launch: the one batch whose preparation the refresh in front of this step had to put off."""

@@ -114,6 +114,19 @@ class Stage1Engine:
         # vertices, triangles, optimizer) and the executor must be rebuilt with it -- train_step checks
         self._captured = (int(model.vertices.shape[0]), int(model.triangles.shape[0]), model.triangles.data_ptr(), id(tr.optimizer))
 
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """The trainer's state: this executor keeps nothing between steps that the trainer does not hold."""
+        sd = self.tr.state_dict()
+        sd["n2m"]["driver"] = "Stage1Engine"
+        return sd
+
+    def load_state_dict(self, sd, model_only=False):
+        """Loads into the trainer, then rebuilds the executor on what the load attached (a new mesh, a new optimizer: see train_step)."""
+        self.tr.load_state_dict(sd, model_only=model_only)
+        if not model_only:
+            self.__init__(self.tr)
+
     def _grow(self, K):
         if K > self.cap:
             self.cap = cap = int(K * 1.25) + 4096

@@ -62,9 +62,23 @@ class FusedAdamAMP(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         state_dict = dict(state_dict)
         extra = state_dict.pop("n2m_amp", None)
+        given = {id(t) for st in state_dict.get("state", {}).values() for t in st.values() if torch.is_tensor(t)}
         super().load_state_dict(state_dict)
+        for p in self._slot:
+            # a state written by torch.optim.Adam (checkpoint.adam_from_torch): no entry for a parameter that never stepped, and a "step"
+            # entry, whose value travels in n2m_amp["steps"]
+            st = self.state[p]
+            st.pop("step", None)
+            for k in ("exp_avg", "exp_avg_sq"):
+                if k not in st:
+                    st[k] = torch.zeros_like(p)
+                elif id(st[k]) in given:       # torch hands a tensor of the right device and dtype through as it is: the moments are this optimizer's own
+                    st[k] = st[k].clone()
         if extra is not None:
-            self.steps.copy_(extra["steps"].to(self.steps.device))
+            steps = torch.zeros_like(self.steps)
+            n = min(steps.numel(), extra["steps"].numel())
+            steps[:n] = extra["steps"].reshape(-1)[:n].to(steps.device, steps.dtype)
+            self.steps.copy_(steps)
             self.scale.fill_(extra["scale"])
             self.growth_tracker.fill_(extra["growth_tracker"])
             self.growth = tuple(extra.get("growth", self.growth))

@@ -1,6 +1,7 @@
 """Minimal stage-0 training loop: the per-iteration behaviour of the reference's Trainer.train_one_epoch /
 train_step / post_train_step (nerf/utils.py:628-823,1132-1211) and main.py:221-241, without its I/O
-(checkpoints, logging, tensorboard, evaluation images stay the reference's Python).
+(logging, tensorboard, evaluation images stay the reference's Python).  Checkpoints are this package's:
+every driver here has state_dict() / load_state_dict(), checkpoint.py writes them in the reference's layout.
 
 One iteration = [every 16th: occupancy refresh] -> sample rays -> render (march, encode, MLPs, composite) -> MSE (+ mask,
 + specular reg) -> scaled backward -> [multi-GPU: gradient all-reduce] -> unscale -> in-place TV gradient -> Adam -> LR step.
@@ -157,6 +158,8 @@ class Stage0Trainer:
         self.overlap_march = True     # ... on a second stream, next to this step's backward + optimizer kernels (single-rank path)
         self.early_march = True       # ... and already at the start of the step (A/B switch; measured equal to issuing it before the backward)
         self._next = None
+        self._pre = None              # what _prepare() met in front of the newest batch's draw (state_dict)
+        self._refreshed = 0           # index of the newest batch whose occupancy refresh has run
 
     @property
     def loss_acc(self):
@@ -236,10 +239,14 @@ class Stage0Trainer:
     def _prepare(self, refresh=True):
         """Occupancy refresh (every 16th step, nerf/utils.py:1155-1156) + next batch + march pass 1 for it."""
         opt, model = self.opt, self.model
-        if refresh and self.global_step % opt.update_extra_interval == 0:
+        if refresh and self.global_step % opt.update_extra_interval == 0 and self._refreshed <= self.global_step:      # (a loaded state may be behind its refresh)
             if self.sync is not None:
                 self.sync.sync_rng_for_grid_update(self.global_step)
             model.update_extra_state()
+            self._refreshed = self.global_step + 1
+        if refresh:               # (a patch batch drawn again belongs to the running step: a checkpoint never starts there)
+            self._pre = (self.gen.get_state(), int(self.num_rays), int(self.last_num_points),
+                         len(self.depth_schedule.log) if self.depth_schedule is not None else None, self.global_step)
         rays_o, rays_d, images, noises, bg = self.batch()
         # sample buffers for the speculative write pass: a quarter above the last batch (adaptive_num_rays steers M towards
         # opt.num_points, nerf/utils.py:796-797); a batch that still does not fit is re-marched exactly by finish()
@@ -441,6 +448,40 @@ class Stage0Trainer:
             # optimizer update (same order as the reference: refresh -> batch -> march), so the GPU never drains at the read-back
             self._next = self._prepare()
         return loss
+
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """The run at a step boundary under the reference's checkpoint keys plus "n2m" (checkpoint.stage0_state): the same entries
+        engine.Stage0Engine writes, so a file of either driver loads into the other.  The batch prepared ahead is not saved; what is saved
+        is the state in front of its draw."""
+        from . import checkpoint
+        sd = checkpoint.stage0_state(self)
+        pre = self._pre if self._next is not None and self._pre is not None and self._pre[4] == self.global_step else None
+        gen, num_rays, last, pos = pre[:4] if pre is not None else (self.gen.get_state(), int(self.num_rays), int(self.last_num_points),
+                                                                    len(self.depth_schedule.log) if self.depth_schedule is not None else None)
+        sd["n2m"].update(driver="Stage0Trainer", batches={
+            "gen": gen.clone(), "num_rays": num_rays, "last_num_points": last, "prepared": int(self.global_step),
+            "refreshed": int(self._refreshed) if self._next is not None and self._refreshed > self.global_step else 0,
+            "depth_schedule": None if self.depth_schedule is None else self.depth_schedule.state_dict(pos)})
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, model_only=False):
+        from . import checkpoint
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(self.device)
+        checkpoint.load_stage0_state(self, sd, model_only)
+        if model_only:
+            return
+        b = checkpoint.batch_state(sd)
+        self._next, self._pre, self._loss_pending = None, None, []
+        self._refreshed = int(b.get("refreshed", 0))
+        self.gen.set_state(b["gen"].cpu())
+        self.num_rays, self.last_num_points = int(b["num_rays"]), int(b["last_num_points"])
+        if (self.depth_schedule is None) != (b.get("depth_schedule") is None):
+            raise ValueError("depth_schedule: the checkpoint and this driver disagree on enable_sparse_depth")
+        if self.depth_schedule is not None:
+            self.depth_schedule.load_state_dict(b["depth_schedule"])
 
     def _tv(self, xyzs, scale, scale_tensor=None):
         """Stand-alone TV pass (TV not folded into the backward: progressive levels, bound > 1 on the unfused path).  scale_tensor: the
@@ -785,13 +826,64 @@ class Stage1Trainer:
         dist.broadcast(f, src=src)
         self._reattach(v, f)
 
-    def _reattach(self, v, f):
+    def _reattach(self, v, f, v_cumsum=None, f_cumsum=None):
         """Re-initialise stage 1 on a new mesh: fresh offsets, accumulators, optimizer, schedule and Laplacian.  The step count, the
         covered-pixel count, the view cache (rays / ground truth / directions do not depend on the mesh) and the background generator
         (its stream goes on, as the reference's does through a refinement) stay."""
         keep = (self.global_step, self.covered_seen, self.view_cache, self._dirs, self.gen)
-        self.__init__(self.model, self.opt, self.poses, v, f, self.device, self.H, self.W, self.rank, self.world, capture=self.capture)
+        self.__init__(self.model, self.opt, self.poses, v, f, self.device, self.H, self.W, self.rank, self.world, capture=self.capture,
+                      v_cumsum=v_cumsum, f_cumsum=f_cumsum)
         self.global_step, self.covered_seen, self.view_cache, self._dirs, self.gen = keep
+
+    # ------------------------------------------------------------------------------------------------ checkpoints
+    def state_dict(self):
+        """The stage-1 run at a step boundary under the reference's checkpoint keys plus "n2m": the mesh itself (after a refinement it is not
+        the one this trainer was built with), the per-face error accumulators, the background generator and the counters; the vertex offsets
+        ride in the model's state_dict, the view order is a function of global_step."""
+        from . import checkpoint
+        model = self.model
+        optimizer, scaler, adam = checkpoint.optimizer_state(self)
+        sd = {"epoch": self.global_step // max(1, len(self.views)), "global_step": int(self.global_step),
+              "stats": getattr(self, "stats", None) or checkpoint.new_stats(), "stage": int(self.opt.stage),
+              "mean_density": float(model.mean_density), "model": model.state_dict(), "optimizer": optimizer,
+              "lr_scheduler": self.scheduler.state_dict(), "scaler": scaler}
+        sd["n2m"] = {"options": checkpoint.plain_options(self.opt), "adam": adam, "driver": "Stage1Trainer", "covered_seen": int(self.covered_seen),
+                     "gen": self.gen.get_state().clone(), "device_rng": checkpoint._device_rng(self.device),
+                     "mesh": {"vertices": model.vertices, "triangles": model.triangles, "v_cumsum": [int(x) for x in model.v_cumsum],
+                              "f_cumsum": [int(x) for x in model.f_cumsum], "triangles_errors": model.triangles_errors,
+                              "triangles_errors_cnt": model.triangles_errors_cnt}}
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, model_only=False):
+        """model_only: the model and mean_density alone (nerf/utils.py:1446-1447) -- how stage 1 starts from a stage-0 file; this trainer's
+        mesh, offsets, optimizer and counters stay as they are.  Otherwise the saved mesh is attached first (_reattach: fresh offsets,
+        accumulators, optimizer, schedule, Laplacian of ITS size), then everything is loaded into it."""
+        from . import checkpoint
+        model = self.model
+        if torch.device(self.device).type == "cuda":
+            torch.cuda.synchronize(self.device)
+        if model_only or "model" not in sd:
+            checkpoint._load_model(model, sd.get("model", sd), True)
+            if "mean_density" in sd:
+                model.mean_density = float(sd["mean_density"])
+            return
+        n2m = sd.get("n2m", {})
+        mesh = n2m.get("mesh")
+        if mesh is None:
+            raise KeyError("n2m.mesh: not a stage-1 checkpoint of this package (a stage-0 file loads with model_only=True)")
+        dev = model.density_bitfield.device
+        self._reattach(mesh["vertices"].to(dev), mesh["triangles"].to(dev), mesh["v_cumsum"], mesh["f_cumsum"])
+        checkpoint._load_model(model, sd["model"], False)
+        model.triangles_errors.copy_(mesh["triangles_errors"].to(dev))
+        model.triangles_errors_cnt.copy_(mesh["triangles_errors_cnt"].to(dev))
+        model.mean_density = float(sd.get("mean_density", 0))
+        checkpoint.load_optimizer_state(self, sd)
+        self.scheduler.load_state_dict(sd.get("lr_scheduler") or {"last_epoch": int(sd["global_step"])})
+        self.global_step, self.covered_seen = int(sd["global_step"]), int(n2m.get("covered_seen", 0))
+        self.stats = sd.get("stats") or checkpoint.new_stats()
+        self.gen.set_state(n2m["gen"].cpu())
+        checkpoint._set_device_rng(self.device, n2m["device_rng"])
 
     @torch.no_grad()
     def refine_mesh(self, src=0, remesh=False, remesh_project=False):

@@ -6,6 +6,9 @@
     tools/evaluate.py --data PATH [--data_format nerf|colmap|dtu] [--split test|val|...]   a captured set: trains on its train split, evaluates --split
     tools/evaluate.py --patch_size 16 [--lambda_patch_ssim w] [--field_only]                stage 0 on patch batches (the autograd trainer)
 
+With a checkpoint of the needed stage in OUT/checkpoints (--ckpt, default latest) the model is loaded instead of trained:
+--iters0 0 / --iters1 0 are then legal, and the stage-1 file brings its mesh with it.
+
 Prints one table row per view and stage, then one JSON line.  LPIPS, the reference's other meter, is not built (no VGG weights here)."""
 import argparse
 import json
@@ -15,7 +18,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from nerf2mesh_amd import export, metrics, synthetic as S
+from nerf2mesh_amd import checkpoint, export, metrics, synthetic as S
 from nerf2mesh_amd.asset import ExportedAsset
 from nerf2mesh_amd.capture import Capture
 from nerf2mesh_amd.engine import Stage0Engine
@@ -40,6 +43,7 @@ ap.add_argument("--size", type=int, default=400, help="synthetic: side of the he
 ap.add_argument("--lambda_ssim", type=float, default=0.0, help="stage 1: weight of 1 - SSIM (0: the reference's loss)")
 ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P x P patches instead of random pixels (1: pixels)")
 ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size >= 11)")
+ap.add_argument("--ckpt", default="latest", help="latest | scratch | best | PATH: a trained model of OUT/checkpoints instead of training")
 ap.add_argument("--field_only", action="store_true", help="stop after the field's evaluation (no mesh, no stage 1, no export)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -47,7 +51,7 @@ torch.manual_seed(0)
 
 opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=True, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
                    patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim,
-                   per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort)
+                   per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort, workspace=args.out)
 model = NeRFNetwork(opt)
 if args.data is None:
     cap, poses = None, S.make_cameras(100, seed=0)
@@ -75,15 +79,22 @@ pixels = args.patch_size == 1 and args.lambda_patch_ssim == 0          # patch b
 cls = Stage0Engine if (cap is None and pixels) or Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
 eng = cls(model, opt, poses, dev, seed=0, capture=cap)
 eng.mark_untrained()
+ckpt0, _ = checkpoint.restore_or_init(eng, args.out, args.ckpt)
+saved_mesh = None if args.field_only else checkpoint.stage1_mesh(args.out, args.ckpt)
+if ckpt0 is None and saved_mesh is None and args.iters0 <= 0:
+    raise SystemExit(f"--iters0 0 needs a stage-0 checkpoint in {os.path.join(args.out, 'checkpoints')}")
+todo0 = 0 if ckpt0 is not None or saved_mesh is not None else args.iters0
 import time
 torch.cuda.synchronize()
 t0 = time.perf_counter()
-for _ in range(args.iters0):
+for _ in range(todo0):
     eng.train_step()
 torch.cuda.synchronize()
-ms0 = (time.perf_counter() - t0) * 1e3 / max(1, args.iters0)
-print(f"[stage 0] {args.iters0} steps ({cls.__name__}, patch_size {args.patch_size}, lambda_patch_ssim {args.lambda_patch_ssim:g}): {ms0:.3f} ms / step, "
-      f"{eng.rays_seen / max(1, args.iters0):.0f} rays / step", flush=True)
+ms0 = (time.perf_counter() - t0) * 1e3 / max(1, todo0)
+if ckpt0 is not None:
+    print(f"[ckpt] stage 0: loaded {ckpt0} (step {eng.global_step}), nothing trained", flush=True)
+print(f"[stage 0] {todo0} steps ({cls.__name__}, patch_size {args.patch_size}, lambda_patch_ssim {args.lambda_patch_ssim:g}): {ms0:.3f} ms / step, "
+      f"{eng.rays_seen / max(1, eng.global_step):.0f} rays / step", flush=True)
 model.eval()
 with eng.averaged_parameters():
     field = metrics.evaluate_views(metrics.field_renderer(model, held), held, views)
@@ -93,17 +104,23 @@ if args.field_only:
                       "lambda_patch_ssim": args.lambda_patch_ssim, "stage0_ms_per_step": round(ms0, 4), "stage0_driver": cls.__name__,
                       "field": {k: field[k] for k in ("psnr", "ssim", "mean_psnr", "mean_ssim")}}))
     sys.exit(0)
-with eng.averaged_parameters():
-    model.export_stage0(os.path.join(args.out, "mesh_stage0"), resolution=args.resolution, **({} if cap is None else dict(dataset=cap, clean=True, decimate=True)))
-rv, rt = export.read_ply(os.path.join(args.out, "mesh_stage0", "mesh_0.ply"))
 opt.stage, opt.iters = 1, max(args.iters1, 501)
-tr = Stage1Trainer(model, opt, poses, torch.from_numpy(rv), torch.from_numpy(rt), dev, capture=cap)
-step = Stage1Engine(tr).train_step if Stage1Engine.supported(tr) else tr.train_step
-for _ in range(args.iters1):
-    step()
+if saved_mesh is not None:              # the stage-1 file brings its mesh with it
+    rt = saved_mesh[1]
+    tr = Stage1Trainer(model, opt, poses, saved_mesh[0], rt, dev, capture=cap, v_cumsum=saved_mesh[2], f_cumsum=saved_mesh[3])
+else:
+    with eng.averaged_parameters():
+        model.export_stage0(os.path.join(args.out, "mesh_stage0"), resolution=args.resolution, **({} if cap is None else dict(dataset=cap, clean=True, decimate=True)))
+    rv, rt = export.read_ply(os.path.join(args.out, "mesh_stage0", "mesh_0.ply"))
+    tr = Stage1Trainer(model, opt, poses, torch.from_numpy(rv), torch.from_numpy(rt), dev, capture=cap)
+drv = Stage1Engine(tr) if Stage1Engine.supported(tr) else tr
+mode1 = checkpoint.restore_or_init(drv, args.out, args.ckpt)[1] if saved_mesh is not None else None
+todo1 = 0 if mode1 == "full" else args.iters1
+for _ in range(todo1):
+    drv.train_step()
 torch.cuda.synchronize()
 model.eval()
-print(f"[pipeline] stage 0: {args.iters0} steps ({cls.__name__}); stage 1: {args.iters1} steps on {rt.shape[0]} faces, lambda_ssim {args.lambda_ssim:g} "
+print(f"[pipeline] stage 0: {todo0} steps ({cls.__name__}); stage 1: {todo1} steps on {rt.shape[0]} faces, lambda_ssim {args.lambda_ssim:g} "
       f"({'executor' if Stage1Engine.supported(tr) else 'autograd trainer'}); {len(views)} held-out views {held.H} x {held.W}", flush=True)
 mesh = metrics.evaluate_views(metrics.mesh_renderer(model, held), held, views)
 out_dir = os.path.join(args.out, "mesh_stage1")

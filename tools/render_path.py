@@ -3,9 +3,12 @@
 
     tools/render_path.py WORKSPACE [--source field|mesh|asset] [--camera_traj circle] [--n_test N] [--video apng]
                                    [--iters0 N --iters1 N --views V --size S [--width W]]          the short synthetic pipeline
+                                   [--ckpt latest|scratch|best|PATH]                               a trained model of WORKSPACE/checkpoints
     tools/render_path.py WORKSPACE --data PATH [--data_format nerf|colmap|dtu] [--downscale k] ...   a captured set (its train split)
 
-Trains stage 0 (and, for --source mesh / asset, extracts the mesh, runs stage 1 and, for asset, exports and loads the files back), builds
+With a checkpoint of the needed stage in WORKSPACE/checkpoints (tools/train_capture.py writes them; --ckpt, default latest) the model is
+loaded and nothing is trained -- --iters0 0 / --iters1 0 are then legal, and for --source mesh / asset the stage-1 file brings its mesh with it.
+Otherwise: trains stage 0 (and, for --source mesh / asset, extracts the mesh, runs stage 1 and, for asset, exports and loads the files back), builds
 the path -- by default the sine-eased interpolation between 5 random training views with N + 1 frames per segment (CameraPath.between),
 with --camera_traj circle the reference's small circle of 100 look-at poses -- renders every frame from the chosen product and writes
 WORKSPACE/results/{name}_{i:04d}_rgb.png and _depth.png; --video apng adds {name}_rgb.apng and {name}_depth.apng (animated PNG: the stand-in
@@ -19,7 +22,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from nerf2mesh_amd import camera_path, export, metrics, synthetic as S
+from nerf2mesh_amd import camera_path, checkpoint, export, metrics, synthetic as S
 from nerf2mesh_amd.asset import ExportedAsset
 from nerf2mesh_amd.capture import Capture
 from nerf2mesh_amd.engine import Stage0Engine
@@ -47,6 +50,7 @@ ap.add_argument("--texture", type=int, default=2048)
 ap.add_argument("--views", type=int, default=100, help="synthetic: training views")
 ap.add_argument("--size", type=int, default=400, help="synthetic: height of the frames (and width, without --width)")
 ap.add_argument("--width", type=int, default=None)
+ap.add_argument("--ckpt", default="latest", help="latest | scratch | best | PATH (default: the newest checkpoint of the workspace, if there is one)")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -73,27 +77,37 @@ else:
 cls = Stage0Engine if Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
 eng = cls(model, opt, None, dev, seed=args.seed, capture=cap)
 eng.mark_untrained()
-for _ in range(args.iters0):
+ckpt0, _ = checkpoint.restore_or_init(eng, args.workspace, args.ckpt)
+saved_mesh = checkpoint.stage1_mesh(args.workspace, args.ckpt) if args.source != "field" else None
+if ckpt0 is None and saved_mesh is None and args.iters0 <= 0:
+    raise SystemExit(f"--iters0 0 needs a stage-0 checkpoint in {os.path.join(args.workspace, 'checkpoints')}")
+todo0 = 0 if ckpt0 is not None or saved_mesh is not None else args.iters0
+for _ in range(todo0):
     eng.train_step()
 torch.cuda.synchronize()
 model.eval()
-print(f"[stage 0] {args.iters0} steps ({cls.__name__}) on {len(cap)} views {cap.H} x {cap.W}", flush=True)
+print(f"[stage 0] {f'loaded {ckpt0} (step {eng.global_step}), ' if ckpt0 is not None else ''}{todo0} steps trained ({cls.__name__}) on {len(cap)} views {cap.H} x {cap.W}", flush=True)
 
 path = camera_path.path_for(cap, opt, n_test=args.n_test, seed=args.seed)
 if args.source != "field":
-    with eng.averaged_parameters():
-        model.export_stage0(os.path.join(args.workspace, "mesh_stage0"), resolution=args.resolution, dataset=cap, clean=True, decimate=True)
-    rv, rt = export.read_ply(os.path.join(args.workspace, "mesh_stage0", "mesh_0.ply"))
-    if rt.shape[0] == 0:
-        raise SystemExit("export_stage0 left no face: stage 0 has not found the object (more --iters0)")
     opt.stage, opt.iters = 1, max(args.iters1, 501)
-    tr = Stage1Trainer(model, opt, None, torch.from_numpy(rv), torch.from_numpy(rt), dev, capture=cap)
-    step = Stage1Engine(tr).train_step if Stage1Engine.supported(tr) else tr.train_step
-    for _ in range(args.iters1):
-        step()
+    if saved_mesh is not None:          # the stage-1 file brings its mesh with it
+        tr = Stage1Trainer(model, opt, None, saved_mesh[0], saved_mesh[1], dev, capture=cap, v_cumsum=saved_mesh[2], f_cumsum=saved_mesh[3])
+    else:
+        with eng.averaged_parameters():
+            model.export_stage0(os.path.join(args.workspace, "mesh_stage0"), resolution=args.resolution, dataset=cap, clean=True, decimate=True)
+        rv, rt = export.read_ply(os.path.join(args.workspace, "mesh_stage0", "mesh_0.ply"))
+        if rt.shape[0] == 0:
+            raise SystemExit("export_stage0 left no face: stage 0 has not found the object (more --iters0)")
+        tr = Stage1Trainer(model, opt, None, torch.from_numpy(rv), torch.from_numpy(rt), dev, capture=cap)
+    drv = Stage1Engine(tr) if Stage1Engine.supported(tr) else tr
+    ckpt1, mode1 = checkpoint.restore_or_init(drv, args.workspace, args.ckpt) if saved_mesh is not None else (None, None)
+    todo1 = 0 if mode1 == "full" else args.iters1
+    for _ in range(todo1):
+        drv.train_step()
     torch.cuda.synchronize()
     model.eval()
-    print(f"[stage 1] {args.iters1} steps on {rt.shape[0]} faces", flush=True)
+    print(f"[stage 1] {f'loaded {ckpt1} (step {tr.global_step}), ' if mode1 == 'full' else ''}{todo1} steps trained on {model.triangles.shape[0]} faces", flush=True)
 
 torch.cuda.synchronize()
 t0 = time.perf_counter()

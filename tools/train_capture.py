@@ -8,6 +8,7 @@
                                                  [--per_view_intrinsics] [--undistort]]
                            [--data_format dtu]
                            [--test [--test_no_video] [--camera_traj circle] [--n_test N]]
+                           [--ckpt latest|scratch|best|PATH] [--n_ckpt N]
 
   colmap: --scale defaults to -1 (1 / the nearest camera's distance), the model's training box is the sparse points' (update_aabb,
   main.py:234-235), --enable_cam_near_far clamps every ray to its view's keypoint depth range, --enable_sparse_depth makes one step in
@@ -29,6 +30,10 @@
   rendered from the stage-1 mesh and written to WORKSPACE/results as {name}_{i:04d}_rgb.png / _depth.png, and as animated PNGs
   ({name}_rgb.apng, {name}_depth.apng: the stand-in for the reference's mp4) unless --test_no_video.
 
+  --ckpt (default latest): each stage resumes from the newest checkpoint of its stage in WORKSPACE/checkpoints and trains the
+  steps that are left of --iters0 / --iters1; without one it starts from scratch (stage 1: from the newest stage-0 file).  --n_ckpt N saves
+  every N steps; every stage saves when it ends.  With --test and a checkpoint present nothing is trained.
+
 Reads nothing but PATH; writes under --workspace.  With --bound > 1 stage 1 refines the inner mesh (cascade 0) only, except under --sdf:
 `--sdf --bound 2` is the SDF recipe on an unbounded scene (contracted background), export_stage0 then writes the outer shell as mesh_1.ply
 and stage 1 loads both files (export.load_stage0_meshes; one cascade when the shell came out empty).  That recipe switches the offset
@@ -43,6 +48,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+from nerf2mesh_amd import checkpoint
 from nerf2mesh_amd.asset import ExportedAsset, evaluate_export, psnr
 from nerf2mesh_amd.capture import Capture
 from nerf2mesh_amd.engine import Stage0Engine
@@ -82,6 +88,8 @@ ap.add_argument("--test", action="store_true", help="after training, render a te
 ap.add_argument("--test_no_video", action="store_true", help="--test: frames only, no animated PNGs")
 ap.add_argument("--camera_traj", choices=["", "circle"], default="", help="--test: the path (default: interpolate between random training views)")
 ap.add_argument("--n_test", type=int, default=24, help="--test: frames per segment of the interpolated path, less one")
+ap.add_argument("--ckpt", default="latest", help="latest | scratch | best | PATH: where each stage starts from (default: the newest checkpoint of the workspace)")
+ap.add_argument("--n_ckpt", type=int, default=0, help="save a checkpoint every N steps (0: only when a stage ends)")
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -146,28 +154,40 @@ if colmap:
 cls = Stage0Engine if Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
 eng = cls(model, opt, None, dev, seed=args.seed, capture=cap)
 eng.mark_untrained()
+ckpt0, mode0 = checkpoint.restore_or_init(eng, args.workspace, args.ckpt)
+todo0 = 0 if args.test and ckpt0 is not None else max(0, args.iters0 - eng.global_step)
+print(f"[ckpt] stage 0: {'from scratch' if ckpt0 is None else f'{ckpt0} ({mode0}) at step {eng.global_step}'}, {todo0} steps to train", flush=True)
 t0 = time.perf_counter()
 tail0 = []                                   # the last training losses of stage 0 (device scalars): what two runs with and without --ind_dim compare
-for _ in range(args.iters0):
+for _ in range(todo0):
     tail0.append(eng.train_step().detach().reshape(()).clone())
     if len(tail0) > 100:
         tail0.pop(0)
+    if args.n_ckpt > 0 and eng.global_step % args.n_ckpt == 0:
+        checkpoint.save_checkpoint(eng, args.workspace)
+if todo0 > 0:
+    checkpoint.save_checkpoint(eng, args.workspace)
 train_loss_tail = float(torch.stack(tail0).mean()) if tail0 else float("nan")
 psnr0 = [eng.eval_psnr(cam=v, downscale=1, use_ema=True, capture=held) for v in views]
-clock("stage 0", t0, f"{args.iters0} steps ({cls.__name__}), held-out PSNR {np.mean(psnr0):.2f} dB")
+clock("stage 0", t0, f"{todo0} steps ({cls.__name__}), held-out PSNR {np.mean(psnr0):.2f} dB")
 
 t0 = time.perf_counter()
-with eng.averaged_parameters():          # the mesh comes from the averaged weights, like the reference's (nerf/utils.py:1340-1341)
-    meshes = model.export_stage0(os.path.join(args.workspace, "mesh_stage0"), resolution=args.resolution, decimate_target=args.decimate_target,
-                                 dataset=cap, clean=True, decimate=True)
-v0, f0 = meshes[0]
-clock("export_stage0", t0, f"{v0.shape[0]} vertices, {f0.shape[0]} triangles (visibility filter, clean, decimate)")
-if f0.shape[0] == 0:
-    raise SystemExit("export_stage0 left no face: stage 0 has not found the object (more --iters0, or check --scale / --bound)")
+saved_mesh = checkpoint.stage1_mesh(args.workspace, args.ckpt)          # a stage-1 checkpoint brings its mesh with it
+if saved_mesh is None:
+    with eng.averaged_parameters():          # the mesh comes from the averaged weights, like the reference's (nerf/utils.py:1340-1341)
+        meshes = model.export_stage0(os.path.join(args.workspace, "mesh_stage0"), resolution=args.resolution, decimate_target=args.decimate_target,
+                                     dataset=cap, clean=True, decimate=True)
+    v0, f0 = meshes[0]
+    clock("export_stage0", t0, f"{v0.shape[0]} vertices, {f0.shape[0]} triangles (visibility filter, clean, decimate)")
+    if f0.shape[0] == 0:
+        raise SystemExit("export_stage0 left no face: stage 0 has not found the object (more --iters0, or check --scale / --bound)")
 
 # ---- stage 1
 opt.stage, opt.iters = 1, max(args.iters1, 501)
-if opt.sdf and model.cascade > 1:          # the contracted recipe: every cascade export_stage0 wrote (mesh_0.ply, and mesh_1.ply unless the shell was empty)
+if saved_mesh is not None:
+    v0, f0, v_cumsum, f_cumsum = saved_mesh
+    tr = Stage1Trainer(model, opt, None, v0, f0, dev, seed=args.seed, capture=cap, v_cumsum=v_cumsum, f_cumsum=f_cumsum)
+elif opt.sdf and model.cascade > 1:          # the contracted recipe: every cascade export_stage0 wrote (mesh_0.ply, and mesh_1.ply unless the shell was empty)
     from nerf2mesh_amd import export
     va, fa, v_cumsum, f_cumsum = export.load_stage0_meshes(os.path.join(args.workspace, "mesh_stage0"), model.cascade)
     print(f"[stage 1] {len(v_cumsum) - 1} cascade(s): vertices {v_cumsum}, faces {f_cumsum}", flush=True)
@@ -175,10 +195,18 @@ if opt.sdf and model.cascade > 1:          # the contracted recipe: every cascad
                        f_cumsum=f_cumsum)
 else:
     tr = Stage1Trainer(model, opt, None, v0, f0, dev, seed=args.seed, capture=cap)
-step = Stage1Engine(tr).train_step if Stage1Engine.supported(tr) else tr.train_step
+drv = Stage1Engine(tr) if Stage1Engine.supported(tr) else tr
+ckpt1, mode1 = checkpoint.restore_or_init(drv, args.workspace, args.ckpt)
+todo1 = 0 if args.test and (mode1 == "full" or ckpt0 is not None) else max(0, args.iters1 - tr.global_step)
+print(f"[ckpt] stage 1: {'from the stage-0 model in memory' if ckpt1 is None else f'{ckpt1} ({mode1}) at step {tr.global_step}'}, {todo1} steps to train", flush=True)
 t0 = time.perf_counter()
-for _ in range(args.iters1):
-    step()
+for _ in range(todo1):
+    drv.train_step()
+    if args.n_ckpt > 0 and tr.global_step % args.n_ckpt == 0:
+        checkpoint.save_checkpoint(drv, args.workspace)
+if todo1 > 0:
+    checkpoint.save_checkpoint(drv, args.workspace)
+f0 = model.triangles
 model.eval()
 psnr1, eval_views = [], []
 with torch.no_grad():
@@ -187,7 +215,7 @@ with torch.no_grad():
         gt = rgba[:, :3] * rgba[:, 3:] + (1 - rgba[:, 3:])
         psnr1.append(psnr(model.render_stage1(None, rays_d, held.mvps[v], held.H, held.W)["image"].view(-1, 3), gt))
         eval_views.append((rays_d, held.mvps[v]))
-clock("stage 1", t0, f"{args.iters1} steps on {f0.shape[0]} faces, held-out PSNR {np.mean(psnr1):.2f} dB")
+clock("stage 1", t0, f"{todo1} steps on {f0.shape[0]} faces, held-out PSNR {np.mean(psnr1):.2f} dB")
 
 t0 = time.perf_counter()
 out_dir = os.path.join(args.workspace, "mesh_stage1")
@@ -209,6 +237,6 @@ depth_steps = sum(v is not None for v in eng.depth_schedule.log[:args.iters0]) i
 if args.enable_dense_depth:
     depth_steps = args.iters0                  # every step carries the depth term
 print(json.dumps({"data_format": args.data_format, "test_frames": test_frames, "ind_dim": args.ind_dim, "train_loss_tail": train_loss_tail, "per_view_intrinsics": bool(cap.per_view_intrinsics), "depth_steps": depth_steps, "train_views": len(cap), "held_out_views": len(views), "held_out_is_test_split": held is not cap, "H": cap.H, "W": cap.W,
-                  "bank_mb": round(cap.nbytes / 1e6, 3), "iters0": args.iters0, "iters1": args.iters1, "faces": int(f0.shape[0]),
+                  "bank_mb": round(cap.nbytes / 1e6, 3), "iters0": args.iters0, "iters1": args.iters1, "trained0": todo0, "trained1": todo1, "resumed0": ckpt0, "resumed1": ckpt1 if mode1 == "full" else None, "faces": int(f0.shape[0]),
                   "psnr_stage0": float(np.mean(psnr0)), "psnr_stage1": float(np.mean(psnr1)), "export_psnr_vs_stage1": ev["mean"],
                   "export_psnr_per_view": ev["psnr_vs_stage1"]}))
