@@ -165,6 +165,26 @@ int n2m_composite_rays_train_backward(const float* grad_weights, const float* gr
                                       uint32_t M, uint32_t N, float T_thresh, int alpha_mode,
                                       float* grad_sigmas, float* grad_rgbs, void* stream);
 
+/* Distortion loss on the ray weights (mip-NeRF 360 eq. 15; not a reference operator -- csrc/distortion.hip).
+ * weights [M] (composite_rays_train's), ts [M,2] = (t after the step, dt), rays [N,2] = (offset, count), nears / fars [N]: the values the
+ * marcher was given.  Sample i of a ray covers [t_i - dt_i, t_i]; its ends are mapped to s(t) = (g(t) - g(near)) / (g(far) - g(near)) with
+ * g(t) = t (N2M_DISTORT_LINEAR) or 1 / t (N2M_DISTORT_DISPARITY), m_i is the mapped interval's midpoint and d_i its length:
+ *     loss_ray[r] = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i,   totals[r] = (sum_i w_i, sum_i w_i m_i)
+ * in O(count) through prefix sums (m is non-decreasing along a ray).  Every ray is written: a ray without samples gets zeros, and so does
+ * a DEGENERATE ray -- far <= near (or either NaN), for which s does not exist -- and a ray cut off by M (offset + count > M, the rays the
+ * compositing kernels skip): 0 loss, 0 totals, 0 gradient.
+ * The backward writes grad_weights[i] = grad_ray[r] * d loss_ray[r] / d w_i for every sample a ray owns inside [0, M) (exact zeros for the
+ * degenerate and the cut-off rays); zero_fill != 0 clears grad_weights first, for callers whose ranges do not tile [0, M) (the contract of
+ * n2m_composite_rays_train_forward's weights).  ts, nears and fars are not differentiated.  One wave per ray, sums in sample order only:
+ * two runs give identical bits.  NULL pointers: N2M_ENULL; M == 0, N == 0 or another space: N2M_EINVAL; all before any launch. */
+#define N2M_DISTORT_LINEAR 0
+#define N2M_DISTORT_DISPARITY 1
+int n2m_distortion_forward(const float* weights, const float* ts, const int32_t* rays, const float* nears, const float* fars,
+                           uint32_t M, uint32_t N, int space, float* loss_ray, float* totals, void* stream);
+int n2m_distortion_backward(const float* weights, const float* ts, const int32_t* rays, const float* nears, const float* fars,
+                            const float* totals, const float* grad_ray, uint32_t M, uint32_t N, int space, int zero_fill,
+                            float* grad_weights, void* stream);
+
 /* raymarching.h:18  march_rays (inference)   kernel raymarching.cu:712-828.
  * Fixed n_step slots per alive ray; xyzs/dirs/ts [n_alive*n_step, .] are caller-zero-filled, a slot with
  * ts[.,0] == 0 is an empty slot.  noises [n_alive]. */

@@ -36,6 +36,8 @@ SIGNATURES = {
     "n2m_grid_backward_mid_event": [_vp],
     "n2m_composite_rays_train_forward": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _int, _vp, _vp, _vp, _vp, _vp],
     "n2m_composite_rays_train_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _int, _vp, _vp, _vp],
+    "n2m_distortion_forward": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _vp, _vp, _vp],
+    "n2m_distortion_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _int, _int, _vp, _vp],
     "n2m_composite_loss_train": [_vp, _vp],
     "n2m_march_rays": [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _int, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_composite_rays": [_u32, _u32, _f32, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

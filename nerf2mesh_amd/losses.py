@@ -163,6 +163,96 @@ def scatter_rows(src, idx, n):
     return _scatter_rows.apply(src, idx, n)
 
 
+DISTORT_SPACES = {"linear": 0, "disparity": 1}        # N2M_DISTORT_LINEAR / N2M_DISTORT_DISPARITY of include/n2m_hip.h
+
+
+class _distortion(Function):
+    """(mean over the N rays, loss_ray [N]) of n2m_distortion_forward; the backward hands n2m_distortion_backward the per-ray gradient
+    grad_mean / N + grad_loss_ray and returns its grad_weights [M]."""
+
+    @staticmethod
+    def forward(ctx, weights, ts, rays, nears, fars, space, tiled):
+        M, N = weights.shape[0], rays.shape[0]
+        dev = weights.device
+        loss_ray = torch.empty(N, dtype=torch.float32, device=dev)
+        totals = torch.empty(N, 2, dtype=torch.float32, device=dev)
+        L.call("n2m_distortion_forward", _p(weights), _p(ts), _p(rays), _p(nears), _p(fars), M, N, space, _p(loss_ray), _p(totals), L.stream())
+        ctx.save_for_backward(weights, ts, rays, nears, fars, totals)
+        ctx.cfg = (M, N, space, bool(tiled))
+        ctx.set_materialize_grads(False)
+        return loss_ray.mean(), loss_ray
+
+    @staticmethod
+    def backward(ctx, grad_mean, grad_ray):
+        weights, ts, rays, nears, fars, totals = ctx.saved_tensors
+        M, N, space, tiled = ctx.cfg
+        if grad_mean is None and grad_ray is None:
+            return None, None, None, None, None, None, None
+        g = None if grad_mean is None else torch.div(grad_mean.float().expand(N), N)      # one launch, contiguous [N]
+        if grad_ray is not None:
+            g = grad_ray.float() if g is None else g + grad_ray.float()
+        grad_weights = torch.empty(M, dtype=torch.float32, device=weights.device)
+        L.call("n2m_distortion_backward", _p(weights), _p(ts), _p(rays), _p(nears), _p(fars), _p(totals), _p(g.contiguous()), M, N, space,
+               int(not tiled), _p(grad_weights), L.stream())
+        return grad_weights, None, None, None, None, None, None
+
+
+def distortion_loss_torch(weights, ts, rays, nears, fars, space="linear", return_per_ray=False):
+    """Torch statement of distortion_loss (any device, float64 inside, differentiable in `weights`): the O(n) form over the packed rays, its
+    segmented running sums taken as one cumulative sum over the owned samples minus its value at each ray's first sample."""
+    if space not in DISTORT_SPACES:
+        raise ValueError(f"distortion_loss: space must be one of {sorted(DISTORT_SPACES)}, got {space!r}")
+    M, N, dev = weights.shape[0], rays.shape[0], weights.device
+    off, cnt = rays[:, 0].long(), rays[:, 1].long()
+    ok = (cnt > 0) & (off >= 0) & (off + cnt <= M) & (fars > nears)          # a ray cut off by M and a degenerate ray contribute nothing
+    cnt = torch.where(ok, cnt, torch.zeros_like(cnt))
+    rid = torch.repeat_interleave(torch.arange(N, device=dev), cnt)          # the ray of every owned sample, ray by ray
+    K = rid.shape[0]
+    if K == 0:
+        loss_ray = weights.sum() * 0 + torch.zeros(N, dtype=torch.float32, device=dev)
+        return (loss_ray.mean(), loss_ray) if return_per_ray else loss_ray.mean()
+    first = torch.cumsum(cnt, 0) - cnt                                       # position of each ray's first sample in that list
+    idx = off[rid] + (torch.arange(K, device=dev) - first[rid])
+    w, t, dt = weights[idx].double(), ts[idx, 0].double(), ts[idx, 1].double()
+    g = (lambda x: 1.0 / x) if space == "disparity" else (lambda x: x)
+    gn, gf = g(nears.double())[rid], g(fars.double())[rid]
+    lo, hi = (g(t - dt) - gn) / (gf - gn), (g(t) - gn) / (gf - gn)
+    m, d = (lo + hi) / 2, (hi - lo).abs()
+    before_w, before_s = torch.cumsum(w, 0) - w, torch.cumsum(w * m, 0) - w * m
+    at = first.clamp(max=K - 1)
+    w_lt, s_lt = before_w - before_w[at][rid], before_s - before_s[at][rid]
+    per = 2 * w * (m * w_lt - s_lt) + w * w * d / 3
+    loss_ray = torch.zeros(N, dtype=torch.float64, device=dev).index_add(0, rid, per).float()
+    return (loss_ray.mean(), loss_ray) if return_per_ray else loss_ray.mean()
+
+
+def distortion_loss(weights, ts, rays, nears, fars, space="linear", rays_tile_samples=False, return_per_ray=False):
+    """Distortion loss of the ray weights (mip-NeRF 360 eq. 15; not a reference loss -- DESIGN 4.30), before its lambda: the mean over ALL N
+    rays of  sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i,  m_i / d_i the midpoint / length of sample i's interval [t_i - dt_i, t_i]
+    in the coordinate s(t) = (g(t) - g(near)) / (g(far) - g(near)), g(t) = t ("linear") or 1 / t ("disparity").
+    weights [M] and ts [M,2] of composite_rays_train / march_rays_train, rays [N,2] = (offset, count), nears / fars [N] as the marcher was
+    given them.  Differentiable in `weights` only.  A ray without samples, a ray cut off by M and a ray with far <= near contribute 0.
+    rays_tile_samples: the ranges of `rays` cover [0, M) without gaps (march_rays_train's do), so the gradient needs no zero-fill.
+    return_per_ray: (mean, loss_ray [N]).  Device tensors run n2m_distortion_forward / _backward, CPU tensors the torch statement."""
+    if space not in DISTORT_SPACES:
+        raise ValueError(f"distortion_loss: space must be one of {sorted(DISTORT_SPACES)}, got {space!r}")
+    M, N = weights.shape[0], rays.shape[0]
+    if weights.dim() != 1 or tuple(ts.shape) != (M, 2) or rays.dim() != 2 or rays.shape[1] != 2 or tuple(nears.shape) != (N,) \
+            or tuple(fars.shape) != (N,):
+        raise ValueError(f"distortion_loss: expected weights [M], ts [M,2], rays [N,2], nears [N], fars [N], got {tuple(weights.shape)}, "
+                         f"{tuple(ts.shape)}, {tuple(rays.shape)}, {tuple(nears.shape)}, {tuple(fars.shape)}")
+    if N == 0:
+        raise ValueError("distortion_loss: no rays")
+    if not weights.is_cuda or M == 0:                      # (the C ABI refuses empty tensors; a batch without samples has loss 0)
+        return distortion_loss_torch(weights, ts, rays, nears, fars, space, return_per_ray)
+    for name, t in (("ts", ts), ("rays", rays), ("nears", nears), ("fars", fars)):
+        if t.device != weights.device:
+            raise RuntimeError(f"distortion_loss: {name} is on {t.device}, weights on {weights.device}")
+    mean, loss_ray = _distortion.apply(weights.float().contiguous(), ts.float().contiguous(), rays.to(torch.int32).contiguous(),
+                                       nears.float().contiguous(), fars.float().contiguous(), DISTORT_SPACES[space], rays_tile_samples)
+    return (mean, loss_ray) if return_per_ray else mean
+
+
 def sparse_depth_loss(pred_depth, gt_depth, depth_weight=None):
     """The sparse-depth term of nerf/utils.py:702-704 before its lambda: mean_n w_n (d_n m_n - g_n m_n)^2 with m = (g > 0).  (The reference
     adds the [N,1] term to its [N] loss and means the [N,N] broadcast; that mean is mean(loss) + lambda * this.)  Torch statement of the depth

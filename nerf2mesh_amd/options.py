@@ -31,7 +31,12 @@ _DEFAULTS = dict(
     lambda_patch_ssim=0,  # not a reference option: weight of 1 - SSIM over the P x P patches of a stage-0 batch (metrics.ssim_patches); needs
                          # patch_size >= 11 and selects the unfused loss branch of trainer.Stage0Trainer.  A name of its own: lambda_ssim is handed
                          # to both stages' options by tools/evaluate.py and stage 0 ignores it
-    camera_traj="",      # main.py:28: the test-time camera path, "" (interpolate between random training views) | "circle" (camera_path.path_for)
+    lambda_distort=0,    # not a reference option (nerf2mesh dropped the term its ancestor torch-ngp carried): weight of the distortion loss of the
+                         # ray weights in stage 0 (losses.distortion_loss); > 0 selects trainer.Stage0Trainer, the step executor
+                         # does not carry the term
+    distort_space="linear",   # not a reference option: the coordinate the sample intervals are normalised in, "linear" (t) | "disparity" (1 / t,
+                         # mip-NeRF 360's choice on unbounded scenes)
+    camera_traj="",     # main.py:28: the test-time camera path, "" (interpolate between random training views) | "circle" (camera_path.path_for)
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")
 )
 

@@ -312,19 +312,29 @@ def march_rays_train_begin(rays_o, rays_d, bound, contract, density_bitfield, C,
     return t
 
 
+class Marched(tuple):
+    """(xyzs, dirs, ts, rays) of march_rays_train_finish -- a plain 4-tuple to every caller -- that also names the nears / fars [N] the
+    marcher was given (losses.distortion_loss normalises the sample intervals with them)."""
+
+    def __new__(cls, xyzs, dirs, ts, rays, nears, fars):
+        self = super().__new__(cls, (xyzs, dirs, ts, rays))
+        self.nears, self.fars = nears, fars
+        return self
+
+
 @torch.no_grad()
 def march_rays_train_finish(t):
     t.event.synchronize()
     M = int(t.host_count[0])
-    rays_o = t.keep[0]
+    rays_o, nears, fars = t.keep[0], t.keep[3], t.keep[4]
     dev = rays_o.device
     torch.cuda.current_stream(dev).wait_event(t.done)       # pass 1 (and a speculative pass 2) may have been issued on another stream
     if t.spec is not None and M <= t.cap:
         xyzs, dirs, ts = t.spec
-        return xyzs[:M], dirs[:M], ts[:M], t.rays
+        return Marched(xyzs[:M], dirs[:M], ts[:M], t.rays, nears, fars)
     xyzs = torch.empty(M, 3, dtype=torch.float32, device=dev)
     dirs = torch.empty(M, 3, dtype=torch.float32, device=dev)
     ts = torch.empty(M, 2, dtype=torch.float32, device=dev)
     if M > 0:
         L.call("n2m_march_rays_train", *t.args, _p(xyzs), _p(dirs), _p(ts), _p(t.rays), _p(t.counter), _p(t.noises), L.stream())
-    return xyzs, dirs, ts, t.rays
+    return Marched(xyzs, dirs, ts, t.rays, nears, fars)

@@ -220,7 +220,10 @@ class NeRFRenderer(nn.Module):
 
         if self.training:
             if ticket is not None:      # a MarchTicket of march_ahead, or the (xyzs, dirs, ts, rays) its finish() returned
-                xyzs, dirs, ts, rays = ticket if isinstance(ticket, tuple) else raymarching.march_rays_train_finish(ticket)
+                marched = ticket if isinstance(ticket, tuple) else raymarching.march_rays_train_finish(ticket)
+                xyzs, dirs, ts, rays = marched
+                # what the marcher was given (a plain 4-tuple from a caller of its own does not say: None)
+                nears, fars = getattr(marched, "nears", None), getattr(marched, "fars", None)
             else:
                 xyzs, dirs, ts, rays = raymarching.march_rays_train(rays_o, rays_d, self.real_bound, self.opt.contract, self.density_bitfield,
                                                                     self.cascade, self.grid_size, nears, fars, perturb, dt_gamma, max_steps)
@@ -260,6 +263,7 @@ class NeRFRenderer(nn.Module):
             weights, weights_sum, depth, image = raymarching.composite_rays_train(sigmas, rgbs, ts, rays, T_thresh, self.opt.sdf,
                                                                                   rays_tile_samples=True)   # our marcher's ranges tile [0, M)
             results.update(num_points=xyzs.shape[0], xyzs=xyzs, speculars=speculars, weights=weights, weights_sum=weights_sum)
+            results.update(ts=ts, rays=rays, nears=nears, fars=fars)      # the batch's intervals and ray table (losses.distortion_loss)
         else:
             weights_sum = torch.zeros(N, dtype=torch.float32, device=device)
             depth = torch.zeros(N, dtype=torch.float32, device=device)

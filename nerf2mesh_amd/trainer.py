@@ -152,8 +152,19 @@ class Stage0Trainer:
                 raise ValueError(f"lambda_patch_ssim > 0 needs patch_size {PATCH_MIN} .. {PATCH_MAX} (one valid 11 x 11 SSIM window per patch), "
                                  f"got patch_size {self.patch_size}")
             self.fused_loss = False
+        # lambda_distort > 0 (not a reference option): lambda_distort * the distortion loss of the batch's ray weights
+        # (losses.distortion_loss), in the coordinate distort_space.  It hangs on composite_rays_train's `weights` output like the entropy
+        # term, so it runs on either loss branch and with pixel, patch and depth batches; the step executor does not carry it.
+        self.lambda_distort = float(getattr(opt, "lambda_distort", 0) or 0)
+        self.distort_space = str(getattr(opt, "distort_space", "linear"))
+        from .losses import DISTORT_SPACES
+        if self.distort_space not in DISTORT_SPACES:
+            raise ValueError(f"distort_space must be one of {sorted(DISTORT_SPACES)}, got {self.distort_space!r}")
+        self.distortion_fn = None     # a stand-in for losses.distortion_loss with its signature (tests put the torch statement here)
+        self.last_distortion = None   # lambda_distort > 0: the term of the last step before its weight, detached (device scalar)
+        self.last_distortion_inputs = None      # ... and the (weights, ts, rays, nears, fars) it was formed from, detached
         self._patch = 0               # the patch size of the batch batch() made last, 0 for a pixel batch
-        self.last_patches = None      # patch mode: (image, gt_rgb) of the last step, detached, both [B,P,P,3], blended on the step's background
+        self.last_patches = None     # patch mode: (image, gt_rgb) of the last step, detached, both [B,P,P,3], blended on the step's background
         self.pipeline = True          # issue march pass 1 of the next batch one step ahead (results are identical)
         self.overlap_march = True     # ... on a second stream, next to this step's backward + optimizer kernels (single-rank path)
         self.early_march = True       # ... and already at the start of the step (A/B switch; measured equal to issuing it before the backward)
@@ -358,6 +369,15 @@ class Stage0Trainer:
             w2 = out["weights_sum"].clamp(1e-5, 1 - 1e-5)
             ent = lambda p: (-p * torch.log2(p) - (1 - p) * torch.log2(1 - p)).mean()
             loss = loss + opt.lambda_entropy * (ent(w) + ent(w2))
+        if self.lambda_distort > 0:
+            from .losses import distortion_loss
+            if out["nears"] is None:
+                raise RuntimeError("train_step: lambda_distort > 0 needs the nears / fars the marcher was given (render() got a bare sample tuple)")
+            term = (self.distortion_fn or distortion_loss)(out["weights"], out["ts"], out["rays"], out["nears"], out["fars"],
+                                                           space=self.distort_space, rays_tile_samples=True)
+            self.last_distortion = term.detach()
+            self.last_distortion_inputs = (out["weights"].detach(), out["ts"], out["rays"], out["nears"], out["fars"])
+            loss = loss + self.lambda_distort * term
         if opt.lambda_specular > 0 and out["speculars"] is not None:
             loss = loss + opt.lambda_specular * (out["speculars"] ** 2).sum(-1).mean()
         if opt.sdf and opt.lambda_eikonal > 0:

@@ -5,6 +5,7 @@
     tools/evaluate.py [--iters0 N --iters1 N --views N --size S --lambda_ssim w]            the short synthetic pipeline (tools/eval_export.py's flow)
     tools/evaluate.py --data PATH [--data_format nerf|colmap|dtu] [--split test|val|...]   a captured set: trains on its train split, evaluates --split
     tools/evaluate.py --patch_size 16 [--lambda_patch_ssim w] [--field_only]                stage 0 on patch batches (the autograd trainer)
+    tools/evaluate.py --lambda_distort w [--distort_space disparity] [--field_only]         stage 0 with the distortion loss (the autograd trainer)
 
 With a checkpoint of the needed stage in OUT/checkpoints (--ckpt, default latest) the model is loaded instead of trained:
 --iters0 0 / --iters1 0 are then legal, and the stage-1 file brings its mesh with it.
@@ -43,6 +44,8 @@ ap.add_argument("--size", type=int, default=400, help="synthetic: side of the he
 ap.add_argument("--lambda_ssim", type=float, default=0.0, help="stage 1: weight of 1 - SSIM (0: the reference's loss)")
 ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P x P patches instead of random pixels (1: pixels)")
 ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size >= 11)")
+ap.add_argument("--lambda_distort", type=float, default=0.0, help="stage 0: weight of the distortion loss of the ray weights (0: off; not a reference option)")
+ap.add_argument("--distort_space", choices=["linear", "disparity"], default="linear", help="--lambda_distort: normalise the sample intervals in t or in 1 / t")
 ap.add_argument("--ckpt", default="latest", help="latest | scratch | best | PATH: a trained model of OUT/checkpoints instead of training")
 ap.add_argument("--field_only", action="store_true", help="stop after the field's evaluation (no mesh, no stage 1, no export)")
 args = ap.parse_args()
@@ -50,7 +53,8 @@ dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 
 opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=True, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
-                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim,
+                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, lambda_distort=args.lambda_distort,
+                   distort_space=args.distort_space,
                    per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort, workspace=args.out)
 model = NeRFNetwork(opt)
 if args.data is None:
@@ -75,7 +79,7 @@ else:
         model.update_aabb(cap.pts_aabb.to(dev))
 
 # ---- stage 0 -> mesh -> stage 1 -> files
-pixels = args.patch_size == 1 and args.lambda_patch_ssim == 0          # patch batches and their SSIM term are the autograd trainer's
+pixels = args.patch_size == 1 and args.lambda_patch_ssim == 0 and args.lambda_distort == 0   # patch batches, their SSIM term and the distortion term are the autograd trainer's
 cls = Stage0Engine if (cap is None and pixels) or Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
 eng = cls(model, opt, poses, dev, seed=0, capture=cap)
 eng.mark_untrained()
@@ -93,7 +97,8 @@ torch.cuda.synchronize()
 ms0 = (time.perf_counter() - t0) * 1e3 / max(1, todo0)
 if ckpt0 is not None:
     print(f"[ckpt] stage 0: loaded {ckpt0} (step {eng.global_step}), nothing trained", flush=True)
-print(f"[stage 0] {todo0} steps ({cls.__name__}, patch_size {args.patch_size}, lambda_patch_ssim {args.lambda_patch_ssim:g}): {ms0:.3f} ms / step, "
+print(f"[stage 0] {todo0} steps ({cls.__name__}, patch_size {args.patch_size}, lambda_patch_ssim {args.lambda_patch_ssim:g}, lambda_distort {args.lambda_distort:g} ({args.distort_space})): "
+      f"{ms0:.3f} ms / step, "
       f"{eng.rays_seen / max(1, eng.global_step):.0f} rays / step", flush=True)
 model.eval()
 with eng.averaged_parameters():
@@ -101,7 +106,8 @@ with eng.averaged_parameters():
 if args.field_only:
     print(f"field: mean PSNR {field['mean_psnr']:.2f}, mean SSIM {field['mean_ssim']:.4f} over {len(views)} held-out views {held.H} x {held.W}")
     print(json.dumps({"views": views, "H": held.H, "W": held.W, "iters0": args.iters0, "patch_size": args.patch_size,
-                      "lambda_patch_ssim": args.lambda_patch_ssim, "stage0_ms_per_step": round(ms0, 4), "stage0_driver": cls.__name__,
+                      "lambda_patch_ssim": args.lambda_patch_ssim, "lambda_distort": args.lambda_distort, "distort_space": args.distort_space,
+                      "stage0_ms_per_step": round(ms0, 4), "stage0_driver": cls.__name__,
                       "field": {k: field[k] for k in ("psnr", "ssim", "mean_psnr", "mean_ssim")}}))
     sys.exit(0)
 opt.stage, opt.iters = 1, max(args.iters1, 501)

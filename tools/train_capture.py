@@ -84,6 +84,8 @@ ap.add_argument("--ind_dim", type=int, default=0, help="per-image appearance cod
 ap.add_argument("--ind_num", type=int, default=500, help="code rows; at least the number of training views")
 ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P x P patches instead of random pixels (the autograd trainer)")
 ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size 11 .. 64)")
+ap.add_argument("--lambda_distort", type=float, default=0.0, help="stage 0: weight of the distortion loss of the ray weights (not a reference option; the autograd trainer)")
+ap.add_argument("--distort_space", choices=["linear", "disparity"], default="linear", help="--lambda_distort: normalise the sample intervals in t or in 1 / t")
 ap.add_argument("--test", action="store_true", help="after training, render a test-time camera path from the stage-1 mesh into WORKSPACE/results")
 ap.add_argument("--test_no_video", action="store_true", help="--test: frames only, no animated PNGs")
 ap.add_argument("--camera_traj", choices=["", "circle"], default="", help="--test: the path (default: interpolate between random training views)")
@@ -146,7 +148,8 @@ opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
                    enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics, undistort=args.undistort,
                    lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf,
-                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, camera_traj=args.camera_traj)
+                   patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, lambda_distort=args.lambda_distort,
+                   distort_space=args.distort_space, camera_traj=args.camera_traj)
 model = NeRFNetwork(opt)
 if colmap:
     model.to(dev)
