@@ -185,6 +185,32 @@ int n2m_distortion_backward(const float* weights, const float* ts, const int32_t
                             const float* totals, const float* grad_ray, uint32_t M, uint32_t N, int space, int zero_fill,
                             float* grad_weights, void* stream);
 
+/* Camera-pose refinement in stage 0 (--optimize_poses; not a reference feature -- csrc/posegrad.hip).
+ * A view's stored pose is camera-to-world [R0 | t0] (poses0 [V,4,4], row-major); delta [V,6] = (omega, tau) per view refines it to
+ * [E(omega) R0 | t0 + tau], E = exp([omega]x) by Rodrigues' formula (the Taylor series of its coefficients below |omega| =
+ * N2M_POSE_SERIES_THETA): a rotation about the camera centre in world axes.
+ *   n2m_pose_apply      poses [V,4,4] from poses0 and delta, one thread per view; the bottom row is copied, and a row of delta that is all
+ *                       zero gives the stored pose back bit for bit.
+ *   n2m_pose_ray_grad   ray6 [N,6] = (g_o, d x g_d) per ray from grad_xyzs [M,3], grad_dirs [M,3] (may be NULL: zeros), ts [M,2] and rays
+ *                       [N,2] = (offset, count) of march_rays_train and the rays' world directions rays_d [N,3]:
+ *                       g_o = sum_i g_i, g_d = sum_i (t_i g_i + h_i) over the ray's samples, t_i = ts[i,0] - ts[i,1] (the parameter the
+ *                       marcher formed xyzs[i] with; ts[i,0] is t after the step).  xyzs [M,3] (may be NULL): the marcher's samples under
+ *                       opt.contract -- g_i is then taken back through the contraction at xyzs[i] first (identity inside the unit
+ *                       box).  A ray without samples, and a ray cut off by M
+ *                       (offset + count > M), gets six zeros.  One wave per ray.
+ *   n2m_pose_view_grad  grad_delta [V,6] = (J_l(omega)^T sum (d x g_d), sum g_o) over the rays i with view[i] == v, J_l the left Jacobian of
+ *                       SO(3) at delta[v].  A view without a ray gets zeros.  view[i] outside [0, V) is SKIPPED: the value is compared with
+ *                       the view numbers, never used as an index.  One wave per view.
+ * No atomics; every sum has a fixed order (lane, then index), so two calls on the same inputs give identical bits -- a permutation of the rays
+ * does not.  The sample depths are not differentiated.  A NULL pointer (other than grad_dirs and xyzs) and V == 0, N == 0 or M == 0: N2M_EINVAL, before
+ * any launch. */
+#define N2M_POSE_SERIES_THETA 1e-2
+int n2m_pose_apply(const float* poses0, const float* delta, uint32_t V, float* poses, void* stream);
+int n2m_pose_ray_grad(const float* grad_xyzs, const float* grad_dirs, const float* xyzs, const float* ts, const int32_t* rays,
+                      const float* rays_d, uint32_t M, uint32_t N, float* ray6, void* stream);
+int n2m_pose_view_grad(const float* ray6, const int32_t* view, const float* delta, uint32_t N, uint32_t V, float* grad_delta,
+                       void* stream);
+
 /* raymarching.h:18  march_rays (inference)   kernel raymarching.cu:712-828.
  * Fixed n_step slots per alive ray; xyzs/dirs/ts [n_alive*n_step, .] are caller-zero-filled, a slot with
  * ts[.,0] == 0 is an empty slot.  noises [n_alive]. */

@@ -143,6 +143,8 @@ def stage0_state(d):
     sd["n2m"] = {"options": plain_options(d.opt), "adam": adam, "samples_seen": int(d.samples_seen), "rays_seen": int(d.rays_seen),
                  "loss_sum": d.loss_acc.detach().reshape(1).clone(), "iter_density": int(model.iter_density), "max_level": int(model.max_level),
                  "device_rng": _device_rng(d.device)}
+    if getattr(d, "refiner", None) is not None:          # optimize_poses: the corrections, their Adam, the stored poses' checksum
+        sd["n2m"]["pose_refine"] = d.refiner.state_dict()
     return sd
 
 
@@ -151,6 +153,10 @@ def load_stage0_state(d, sd, model_only=False):
     if "model" not in sd:                       # a bare model state_dict, as the reference accepts one (nerf/utils.py:1423-1426)
         _load_model(model, sd, True)
         return
+    refiner = getattr(d, "refiner", None)
+    if not model_only and (refiner is None) != (sd.get("n2m", {}).get("pose_refine") is None):
+        raise ValueError("pose_refine: the checkpoint and this driver disagree on optimize_poses -- a run with refined poses continues only "
+                         "as one (its field was trained on them); model_only=True takes the model alone")
     _load_model(model, sd["model"], model_only)
     if d.ema is not None and sd.get("ema") is not None:
         d.ema.load_state_dict(sd["ema"])
@@ -171,6 +177,8 @@ def load_stage0_state(d, sd, model_only=False):
     model.max_level = int(n2m.get("max_level", model.max_level))
     if "device_rng" in n2m:
         _set_device_rng(d.device, n2m["device_rng"])
+    if refiner is not None:
+        refiner.load_state_dict(n2m["pose_refine"])      # (refreshes the pose table the driver reads)
 
 
 def batch_state(sd):

@@ -360,7 +360,7 @@ class Stage0Engine:
         return (bool(getattr(opt, "fused_mlp", False)) and bool(opt.fp16) and ind_ok
                 and _affine(float(model.bound)) is not None and same_geometry(e1, e2) and e1.embeddings.shape[1] == 1
                 and e2.embeddings.shape[1] == 2 and (sdf or not getattr(opt, "progressive_level", False))
-                and opt.patch_size == 1 and not float(getattr(opt, "lambda_patch_ssim", 0) or 0) > 0 and not float(getattr(opt, "lambda_distort", 0) or 0) > 0 and (sdf or model.max_level >= e1.num_levels) and not (sdf and opt.lambda_entropy > 0)
+                and opt.patch_size == 1 and not float(getattr(opt, "lambda_patch_ssim", 0) or 0) > 0 and not float(getattr(opt, "lambda_distort", 0) or 0) > 0 and not bool(getattr(opt, "optimize_poses", False)) and (sdf or model.max_level >= e1.num_levels) and not (sdf and opt.lambda_entropy > 0)
                 and not (sdf and (getattr(opt, "enable_sparse_depth", False) or getattr(opt, "enable_dense_depth", False))))      # the depth term is built for density mode
 
     @property

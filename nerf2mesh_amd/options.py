@@ -36,6 +36,9 @@ _DEFAULTS = dict(
                          # does not carry the term
     distort_space="linear",   # not a reference option: the coordinate the sample intervals are normalised in, "linear" (t) | "disparity" (1 / t,
                          # mip-NeRF 360's choice on unbounded scenes)
+    optimize_poses=False,     # not a reference option: stage 0 trains a correction (omega, tau) per camera next to the field
+                         # (pose_refine.PoseRefiner); needs a captured set and the unfused field, selects trainer.Stage0Trainer
+    lr_pose=1e-3,        # not a reference option: the learning rate of those corrections (Adam of its own, the field's schedule)
     camera_traj="",     # main.py:28: the test-time camera path, "" (interpolate between random training views) | "circle" (camera_path.path_for)
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")
 )

@@ -150,6 +150,9 @@ class NeRFRenderer(nn.Module):
         self.iter_density = 0
         self._cell_unit = None      # cached [H^3,3] cell centres in [-1,1], Morton order
         self.glctx = None
+        # opt-in hook (pose refinement): a callable (xyzs, dirs, ts, rays, rays_d, index) -> (xyzs, dirs) that render() runs on a
+        # training batch's samples right before the field is evaluated; the values stay, the gradients find their way to the cameras
+        self.ray_attach = None
 
     def get_params(self, lr):
         params = []
@@ -244,6 +247,8 @@ class NeRFRenderer(nn.Module):
                 ind_code = self.ind_code(sample_views(rays, idx, xyzs.shape[0]) if idx.numel() > 1 else idx.expand(xyzs.shape[0]).contiguous())
             elif ind_code is not None and ind_code.shape[0] > 1:
                 ind_code = ind_code[raymarching.flatten_rays(rays, xyzs.shape[0]).long()]
+            if self.ray_attach is not None:      # (in front of safe_normalize: the gradient wanted is the raw direction's, the one the pose turns)
+                xyzs, dirs = self.ray_attach(xyzs, dirs, ts, rays, rays_d, index)
             in_kernel = hasattr(self, "_can_fuse") and self._can_fuse(ind_code)      # fused field: safe_normalize happens on load
             if not in_kernel:
                 dirs = safe_normalize(dirs)

@@ -47,6 +47,11 @@ class LambdaLR:
         self._apply()
 
 
+def lr_schedule(iters):
+    """The stage-0 learning-rate factor of main.py:239: a linear warm-up from 1 % over 500 steps, then a decay to 0.1 at `iters`."""
+    return lambda it: 0.01 + 0.99 * (it / 500) if it <= 500 else 0.1 ** ((it - 500) / (iters - 500))
+
+
 class Stage0Trainer:
     def __init__(self, model, opt, poses, device, rank=0, world_size=1, seed=0, ema_decay=0.95, capture=None):
         self.model, self.opt, self.device = model.to(device), opt, device
@@ -107,8 +112,7 @@ class Stage0Trainer:
         else:
             self.optimizer = torch.optim.Adam(model.get_params(opt.lr), eps=1e-15, fused=(device.type == "cuda"))
         iters = opt.iters
-        self.scheduler = LambdaLR(
-            self.optimizer, lambda it: 0.01 + 0.99 * (it / 500) if it <= 500 else 0.1 ** ((it - 500) / (iters - 500)))   # main.py:239
+        self.scheduler = LambdaLR(self.optimizer, lr_schedule(iters))   # main.py:239
         self.scaler = torch.amp.GradScaler("cuda", enabled=bool(opt.fp16) and device.type == "cuda")
         self.sync = GradSync(model, world_size) if world_size > 1 else None
         if world_size > 1:      # the occupancy refresh's density query sharded over the ranks by Morton range (renderer.update_extra_state)
@@ -171,6 +175,28 @@ class Stage0Trainer:
         self._next = None
         self._pre = None              # what _prepare() met in front of the newest batch's draw (state_dict)
         self._refreshed = 0           # index of the newest batch whose occupancy refresh has run
+        # optimize_poses (not a reference option): a correction (omega, tau) per view is trained next to the field
+        # (pose_refine.PoseRefiner).  self.poses IS the refiner's buffer, refreshed behind every optimizer step; batch() reads it per batch, so
+        # no batch kernel changes.  The samples' gradients reach the corrections through model.ray_attach, which needs every ray's view
+        # (the batch_views path of the per-image codes).  A batch must be drawn AFTER the poses it is drawn from: no batch is prepared a
+        # step ahead (pipeline = False), which puts the sample-count read-back and the batch kernels back on the step's critical path.
+        self.refiner = None
+        self._stepper = self.optimizer          # what the GradScaler unscales and steps
+        if bool(getattr(opt, "optimize_poses", False)):
+            if capture is None:
+                raise ValueError("optimize_poses needs a captured image set: the analytic scene's poses are exact")
+            if bool(getattr(opt, "fused_mlp", False)):
+                raise ValueError("optimize_poses needs fused_mlp=False: the fused field has no position gradient")
+            if bool(opt.sdf):
+                raise ValueError("optimize_poses with sdf=True is not supported: finite-difference normals under a second-order graph are untested")
+            if world_size > 1:
+                raise ValueError("optimize_poses is not supported on more than one rank")
+            from .pose_refine import JointStep, PoseRefiner
+            self.refiner = PoseRefiner(self.poses, lr=float(getattr(opt, "lr_pose", 1e-3)), iters=opt.iters, contract=bool(opt.contract))
+            self.poses = self.refiner.poses()
+            self.model.ray_attach = self.refiner.attach
+            self._stepper = JointStep(self.optimizer, self.refiner.optimizer)
+            self.pipeline = False
 
     @property
     def loss_acc(self):
@@ -210,7 +236,7 @@ class Stage0Trainer:
                                                                                      cap.intrinsics_of(view), cam_near_far=self.cam_near_far)
             self._depth = (gtd, dw)
             self._nears_fars = (nears, fars) if self.cam_near_far is not None else None
-            if self.ind_codes:
+            if self.ind_codes or self.refiner is not None:
                 self._index = torch.full((u.shape[0],), int(view), dtype=torch.int32, device=self.device)
             return rays_o, rays_d, rgba, noises, bg
         P = self.patch_size
@@ -219,7 +245,7 @@ class Stage0Trainer:
             u = torch.rand(max(1, self.num_rays // (P * P)) * P * P, 6, device=self.device, generator=self.gen)
         else:
             u = torch.rand(self.num_rays, 6, device=self.device, generator=self.gen)
-        if self.ind_codes:
+        if self.ind_codes or self.refiner is not None:
             from .capture import batch_views
             self._index = batch_views(u, len(cap), patch_size=P)     # the same draw, the same expression: the views the batch kernel reads
         if self.dense_depth is not None:
@@ -308,6 +334,8 @@ class Stage0Trainer:
         self._next = None
         self.global_step += 1
         self.optimizer.zero_grad(set_to_none=True)
+        if self.refiner is not None:
+            self.refiner.optimizer.zero_grad(set_to_none=True)
         N = rays_o.shape[0]
         if opt.sdf:
             opt.cos_anneal_ratio = min(1, self.global_step / (0.5 * opt.iters))
@@ -407,6 +435,8 @@ class Stage0Trainer:
                           scale=scale_t, done=False, rows=M)
             model.encoder.tv_request = tv_req
         xyzs = out["xyzs"]
+        if self.refiner is not None:
+            xyzs = xyzs.detach()                               # (the TV pass wants the positions, not their graph)
         if self.amp_adam:
             o = self.optimizer
             self._amp = {"density": dict(found_inf=o.found_inf, flagged=False), "color": dict(found_inf=o.found_inf, flagged=False, keep_half=True),
@@ -445,7 +475,7 @@ class Stage0Trainer:
             model.encoder.tv_request = None
             tv_pending = tv_req is None or not tv_req["done"]
             if self.sync is None:
-                self.scaler.unscale_(self.optimizer)                         # nerf/utils.py:812
+                self.scaler.unscale_(self._stepper)                          # nerf/utils.py:812 (pose refinement: both optimizers, one verdict)
                 if tv_pending:
                     self._tv(xyzs, 1.0)
             else:
@@ -455,9 +485,12 @@ class Stage0Trainer:
                     self._tv(xyzs, self.scaler.get_scale() if self.scaler.is_enabled() else 1.0)
                 self.sync.all_reduce()
                 self.scaler.unscale_(self.optimizer)
-            self.scaler.step(self.optimizer)
+            self.scaler.step(self._stepper)
             self.scaler.update()
         self.scheduler.step()
+        if self.refiner is not None:
+            self.refiner.scheduler.step()
+            self.refiner.poses()                               # the table the next batch is drawn from (self.poses is this buffer)
         if self.ema is not None and self.global_step % self.epoch_len == 0:      # end of an epoch (nerf/utils.py:1213-1214)
             self.ema.update()
         self._loss_pending.append(loss.detach())       # summed lazily (loss_acc): no per-step add kernel

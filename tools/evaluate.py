@@ -6,6 +6,7 @@
     tools/evaluate.py --data PATH [--data_format nerf|colmap|dtu] [--split test|val|...]   a captured set: trains on its train split, evaluates --split
     tools/evaluate.py --patch_size 16 [--lambda_patch_ssim w] [--field_only]                stage 0 on patch batches (the autograd trainer)
     tools/evaluate.py --lambda_distort w [--distort_space disparity] [--field_only]         stage 0 with the distortion loss (the autograd trainer)
+    tools/evaluate.py --data PATH --optimize_poses [--lr_pose r]                            stage 0 refines the camera poses (writes OUT/poses_refined.npy)
 
 With a checkpoint of the needed stage in OUT/checkpoints (--ckpt, default latest) the model is loaded instead of trained:
 --iters0 0 / --iters1 0 are then legal, and the stage-1 file brings its mesh with it.
@@ -17,6 +18,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
 import torch
 
 from nerf2mesh_amd import checkpoint, export, metrics, synthetic as S
@@ -46,15 +48,19 @@ ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P
 ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size >= 11)")
 ap.add_argument("--lambda_distort", type=float, default=0.0, help="stage 0: weight of the distortion loss of the ray weights (0: off; not a reference option)")
 ap.add_argument("--distort_space", choices=["linear", "disparity"], default="linear", help="--lambda_distort: normalise the sample intervals in t or in 1 / t")
+ap.add_argument("--optimize_poses", action="store_true", help="stage 0: train a correction per camera next to the field (needs --data; the autograd trainer, unfused field)")
+ap.add_argument("--lr_pose", type=float, default=1e-3, help="--optimize_poses: learning rate of the corrections")
 ap.add_argument("--ckpt", default="latest", help="latest | scratch | best | PATH: a trained model of OUT/checkpoints instead of training")
 ap.add_argument("--field_only", action="store_true", help="stop after the field's evaluation (no mesh, no stage 1, no export)")
 args = ap.parse_args()
+if args.optimize_poses and args.data is None:
+    ap.error("--optimize_poses needs --data (the synthetic scene's poses are exact)")
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 
-opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=True, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
+opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=not args.optimize_poses, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
                    patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, lambda_distort=args.lambda_distort,
-                   distort_space=args.distort_space,
+                   distort_space=args.distort_space, optimize_poses=args.optimize_poses, lr_pose=args.lr_pose,
                    per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort, workspace=args.out)
 model = NeRFNetwork(opt)
 if args.data is None:
@@ -79,7 +85,7 @@ else:
         model.update_aabb(cap.pts_aabb.to(dev))
 
 # ---- stage 0 -> mesh -> stage 1 -> files
-pixels = args.patch_size == 1 and args.lambda_patch_ssim == 0 and args.lambda_distort == 0   # patch batches, their SSIM term and the distortion term are the autograd trainer's
+pixels = args.patch_size == 1 and args.lambda_patch_ssim == 0 and args.lambda_distort == 0 and not args.optimize_poses   # patch batches, their SSIM term, the distortion term and pose refinement are the autograd trainer's
 cls = Stage0Engine if (cap is None and pixels) or Stage0Engine.supported(model, opt, capture=cap) else Stage0Trainer
 eng = cls(model, opt, poses, dev, seed=0, capture=cap)
 eng.mark_untrained()
@@ -100,6 +106,13 @@ if ckpt0 is not None:
 print(f"[stage 0] {todo0} steps ({cls.__name__}, patch_size {args.patch_size}, lambda_patch_ssim {args.lambda_patch_ssim:g}, lambda_distort {args.lambda_distort:g} ({args.distort_space})): "
       f"{ms0:.3f} ms / step, "
       f"{eng.rays_seen / max(1, eng.global_step):.0f} rays / step", flush=True)
+if args.optimize_poses:
+    # the export and stage 1 see the training views where stage 0 left them; held-out views have no correction
+    cap = eng.refiner.refined(cap)
+    os.makedirs(args.out, exist_ok=True)
+    np.save(os.path.join(args.out, "poses_refined.npy"), cap.poses.cpu().numpy())
+    print(f"[poses] refined poses of {len(cap)} training views -> {os.path.join(args.out, 'poses_refined.npy')}; held-out views are evaluated with "
+          f"their stored poses", flush=True)
 model.eval()
 with eng.averaged_parameters():
     field = metrics.evaluate_views(metrics.field_renderer(model, held), held, views)

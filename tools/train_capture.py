@@ -86,6 +86,8 @@ ap.add_argument("--patch_size", type=int, default=1, help="stage 0: batches of P
 ap.add_argument("--lambda_patch_ssim", type=float, default=0.0, help="stage 0: weight of 1 - SSIM over the batch's patches (needs --patch_size 11 .. 64)")
 ap.add_argument("--lambda_distort", type=float, default=0.0, help="stage 0: weight of the distortion loss of the ray weights (not a reference option; the autograd trainer)")
 ap.add_argument("--distort_space", choices=["linear", "disparity"], default="linear", help="--lambda_distort: normalise the sample intervals in t or in 1 / t")
+ap.add_argument("--optimize_poses", action="store_true", help="stage 0: train a correction (rotation, translation) per camera next to the field (not a reference option; the autograd trainer, unfused field)")
+ap.add_argument("--lr_pose", type=float, default=1e-3, help="--optimize_poses: learning rate of the corrections")
 ap.add_argument("--test", action="store_true", help="after training, render a test-time camera path from the stage-1 mesh into WORKSPACE/results")
 ap.add_argument("--test_no_video", action="store_true", help="--test: frames only, no animated PNGs")
 ap.add_argument("--camera_traj", choices=["", "circle"], default="", help="--test: the path (default: interpolate between random training views)")
@@ -111,6 +113,8 @@ if not colmap and (args.enable_sparse_depth or args.enable_dense_depth or args.e
              "points supply them)")
 if args.enable_sparse_depth and args.enable_dense_depth:
     ap.error("--enable_sparse_depth and --enable_dense_depth exclude each other")
+if args.optimize_poses and args.sdf:
+    ap.error("--optimize_poses does not run with --sdf")
 
 
 def clock(label, t0, extra=""):
@@ -143,13 +147,13 @@ clock("load", t0, f"{len(cap)} training views {cap.H} x {cap.W} ({cap.nbytes / 1
       f"{len(held) if held is not cap else 0} held-out views")
 
 # ---- stage 0
-opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 1 / 256, iters=args.iters0, fused_mlp=True, scale=args.scale,
+opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 1 / 256, iters=args.iters0, fused_mlp=not args.optimize_poses, scale=args.scale,
                    offset=list(args.offset), color_space=args.color_space, decimate_target=args.decimate_target, workspace=args.workspace,
                    data_format=args.data_format, enable_sparse_depth=args.enable_sparse_depth, enable_dense_depth=args.enable_dense_depth,
                    enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics, undistort=args.undistort,
                    lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf,
                    patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, lambda_distort=args.lambda_distort,
-                   distort_space=args.distort_space, camera_traj=args.camera_traj)
+                   distort_space=args.distort_space, optimize_poses=args.optimize_poses, lr_pose=args.lr_pose, camera_traj=args.camera_traj)
 model = NeRFNetwork(opt)
 if colmap:
     model.to(dev)
@@ -173,6 +177,14 @@ if todo0 > 0:
 train_loss_tail = float(torch.stack(tail0).mean()) if tail0 else float("nan")
 psnr0 = [eng.eval_psnr(cam=v, downscale=1, use_ema=True, capture=held) for v in views]
 clock("stage 0", t0, f"{todo0} steps ({cls.__name__}), held-out PSNR {np.mean(psnr0):.2f} dB")
+if args.optimize_poses:
+    # the mesh export, stage 1 and the camera paths see the training views where stage 0 left them; held-out views have no correction
+    cap = eng.refiner.refined(cap)
+    os.makedirs(args.workspace, exist_ok=True)
+    np.save(os.path.join(args.workspace, "poses_refined.npy"), cap.poses.cpu().numpy())
+    moved = eng.refiner.delta.detach().abs().amax(0).cpu().numpy()
+    print(f"[poses] refined poses of {len(cap)} training views -> {os.path.join(args.workspace, 'poses_refined.npy')} (largest |omega| component "
+          f"{moved[:3].max():.3g} rad, largest |tau| component {moved[3:].max():.3g}); held-out views are evaluated with their stored poses", flush=True)
 
 t0 = time.perf_counter()
 saved_mesh = checkpoint.stage1_mesh(args.workspace, args.ckpt)          # a stage-1 checkpoint brings its mesh with it
