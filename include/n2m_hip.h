@@ -211,6 +211,32 @@ int n2m_pose_ray_grad(const float* grad_xyzs, const float* grad_dirs, const floa
 int n2m_pose_view_grad(const float* ray6, const int32_t* view, const float* delta, uint32_t N, uint32_t V, float* grad_delta,
                        void* stream);
 
+/* TSDF fusion of per-view depth maps (--mesh_method tsdf; not a reference operator -- csrc/tsdf.hip).
+ * tsdf, weight [R0,R1,R2] fp32, indexed [x,y,z] with z contiguous (the layout n2m_marching_cubes_* read), updated in place.  Lattice point
+ * (a,b,c) sits at x_k = lo_k + (float)index_k * step_k with step_k = (hi_k - lo_k) / (float)(R_k - 1), formed once on the host in fp32:
+ * linspace(lo, hi, R) per axis.  lo_host, hi_host: HOST arrays of 3 floats.  cams [n,16] (device): per view the camera-to-world rotation
+ * R[0..8] row-major (R[3 j + k] = row j, column k), the centre c[0..2], then fx, fy, cx, cy.  The camera looks down its -z axis, y up, and
+ * pixel (row j, column i) has its centre at (i + 0.5, j + 0.5) (capture.rays_from_pixels; its ray directions have |z| = 1, so the
+ * renderer's t is the depth along the optical axis, the quantity the maps hold).  depth [n,H,W] (device).
+ * Per lattice point x, views v = 0 .. n-1 in this order; every operation is one correctly rounded fp32 operation (no FMA: the library is
+ * built with -ffp-contract=off), sums associated left to right as written:
+ *     d   = x - c                                                   (per component)
+ *     p_k = (R[k] * d_0 + R[3 + k] * d_1) + R[6 + k] * d_2          (p = R^T d, the point in camera axes)
+ *     zc  = -p_2                                                    skip the view unless zc > min_depth
+ *     col = (fx * p_0) / zc + cx,   row = cy - (fy * p_1) / zc      skip unless 0 <= col < W and 0 <= row < H
+ *     i = floor(col), j = floor(row),  dm = depth[v, j, i]          skip unless dm > 0: 0, negatives and NaN all mean "no information"
+ *     sdf = dm - zc                                                 skip if sdf < -trunc
+ *     s   = min(1, sdf / trunc)
+ *     tsdf = (tsdf * w + s) / (w + 1),   w = min(w + 1, w_max)
+ * +inf is a valid depth: the ray stops at nothing, and the view carves the point with s = 1.  A fresh volume is tsdf = 1, weight = 0.
+ * One thread per lattice point walks all n views with (tsdf, w) in registers: the volumes are read and written once per call, the
+ * accumulation per point is sequential in v, so two runs give identical bits and so does any split of the views over calls.  No atomics.
+ * NULL pointers: N2M_ENULL.  n == 0, H == 0, W == 0, H or W >= 2^24, an R below 2, trunc <= 0, w_max < 1, min_depth < 0 (or any of the
+ * three NaN), hi_k <= lo_k on an axis, or R0 R1 R2 >= 2^32: N2M_EINVAL.  All before any launch. */
+int n2m_tsdf_integrate(float* tsdf, float* weight, uint32_t R0, uint32_t R1, uint32_t R2, const float* lo_host, const float* hi_host,
+                       const float* cams, const float* depth, uint32_t n, uint32_t H, uint32_t W, float trunc, float min_depth,
+                       float w_max, void* stream);
+
 /* raymarching.h:18  march_rays (inference)   kernel raymarching.cu:712-828.
  * Fixed n_step slots per alive ray; xyzs/dirs/ts [n_alive*n_step, .] are caller-zero-filled, a slot with
  * ts[.,0] == 0 is an empty slot.  noises [n_alive]. */

@@ -41,6 +41,7 @@ SIGNATURES = {
     "n2m_pose_apply": [_vp, _vp, _u32, _vp, _vp],
     "n2m_pose_ray_grad": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp],
     "n2m_pose_view_grad": [_vp, _vp, _vp, _u32, _u32, _vp, _vp],
+    "n2m_tsdf_integrate": [_vp, _vp, _u32, _u32, _u32, ctypes.POINTER(_f32), ctypes.POINTER(_f32), _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp],
     "n2m_composite_loss_train": [_vp, _vp],
     "n2m_march_rays": [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _int, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "n2m_composite_rays": [_u32, _u32, _f32, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

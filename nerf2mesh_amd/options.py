@@ -39,7 +39,12 @@ _DEFAULTS = dict(
     optimize_poses=False,     # not a reference option: stage 0 trains a correction (omega, tau) per camera next to the field
                          # (pose_refine.PoseRefiner); needs a captured set and the unfused field, selects trainer.Stage0Trainer
     lr_pose=1e-3,        # not a reference option: the learning rate of those corrections (Adam of its own, the field's schedule)
-    camera_traj="",     # main.py:28: the test-time camera path, "" (interpolate between random training views) | "circle" (camera_path.path_for)
+    mesh_method="density",    # not a reference option (it always thresholds the density lattice): how export_stage0 finds the inner mesh, "density" |
+                         # "tsdf" (TSDF fusion of the depth rendered at every training camera: tsdf.py; needs a captured set)
+    tsdf_trunc=0,        # not a reference option: the truncation distance of that fusion in world units; 0: four lattice spacings
+    tsdf_carve=False,    # not a reference option: rays that stop at nothing (opacity < 0.05) mark every point along them as empty
+    tsdf_alpha_min=0.5,  # not a reference option: the least opacity at which a ray's depth counts as a surface observation
+    camera_traj="",    # main.py:28: the test-time camera path, "" (interpolate between random training views) | "circle" (camera_path.path_for)
     scene="lego",        # not a reference option: which synthetic stand-in the drivers render (nerf2mesh_amd/synthetic.py: "lego" | "garden")
 )
 

@@ -279,6 +279,7 @@ class NeRFRenderer(nn.Module):
             else:
                 self._infer_loop_host(rays_o, rays_d, nears, fars, ind_code, shading, dt_gamma, max_steps, T_thresh, perturb, amp,
                                       weights_sum, depth, image)
+            results["weights_sum"] = weights_sum.view(*prefix)      # the rays' opacity, next to "depth" = sum of w t (tsdf.surface_depth)
 
         if blend_bg:       # blend_bg=False: the caller folds the blend into its loss kernel (losses.photo_loss)
             image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
@@ -562,7 +563,8 @@ class NeRFRenderer(nn.Module):
         return vol
 
     @torch.no_grad()
-    def export_stage0(self, save_path, resolution=None, decimate_target=1e5, dataset=None, S=128, decimate=False, clean=False):
+    def export_stage0(self, save_path, resolution=None, decimate_target=1e5, dataset=None, S=128, decimate=False, clean=False,
+                      method="density", tsdf=None):
         """Stage-0 mesh extraction (nerf/renderer.py:472-672): density volume -> marching cubes -> mesh_{cas}.ply.  The volume never leaves
         the device: the reference copies it to the host for PyMCubes (:518); here marching cubes is a HIP kernel (marching_cubes.py).
         clean=True runs the device clean_mesh of mesh_clean.py where the reference runs pymeshlab's (merging close vertices, removing
@@ -581,30 +583,48 @@ class NeRFRenderer(nn.Module):
         that branch did not run.  A shell that any removal empties is skipped -- no file, no key, like an emptied density-mode cascade --
         and stage 1 then has ONE cascade: its loader (export.load_stage0_meshes) stops at the first missing mesh_{cas}.ply.
         dataset: object with `.mvps [B,4,4]`, `.H`, `.W` for the visibility test, or None.
+        method="tsdf" (not a reference path; the default "density" is the path above, untouched): the inner mesh's volume and marching
+        cubes are replaced by TSDF fusion (tsdf.py) -- the field's inference render gives a depth map at every view of
+        `dataset`, which must be a capture.Capture then; the maps are fused into a TSDFVolume(resolution) on the unit box and its zero
+        level set, minus what no view observed, goes on through the visibility filter, cleaning, decimation and the PLY as before.  The
+        outer cascades of bound > 1 still come from the occupancy grid.  tsdf: a dict of TSDFVolume's (trunc, w_max, min_depth),
+        surface_depth's (alpha_min, carve, alpha_carve) and fuse_views' (chunk) keywords.  The SDF recipe already meshes a signed distance:
+        opt.sdf with method="tsdf" raises ValueError.
         Returns {cascade: (vertices [V,3] f32, triangles [F,3] i32)} (device tensors)."""
         import os
         from . import export
         from .marching_cubes import marching_cubes
         from .mesh_clean import clean_mesh
         from .mesh_simplify import decimate as decimate_mesh
+        if method not in ("density", "tsdf"):
+            raise ValueError(f"export_stage0: method must be 'density' or 'tsdf', got {method!r}")
+        if method == "tsdf":
+            from .capture import Capture
+            if self.opt.sdf:
+                raise ValueError("export_stage0: method='tsdf' is for the density recipe; the SDF recipe (opt.sdf) already meshes a signed distance")
+            if not isinstance(dataset, Capture):
+                raise ValueError("export_stage0: method='tsdf' renders a depth map at every training camera and needs dataset=<capture.Capture>")
         dec_target = int(decimate_target) if decimate and decimate_target > 0 else 0     # 0: no decimation
         os.makedirs(save_path, exist_ok=True)
         dev = self.density_bitfield.device
         if resolution is None:
             resolution = self.grid_size
         density_thresh = min(self.mean_density, self.density_thresh)
-        if resolution == self.grid_size:
-            sigmas = self._grid_as_volume(0)
+        if method == "tsdf":
+            vertices, triangles = self._tsdf_inner_mesh(resolution, dataset, tsdf)
         else:
-            sigmas = self.density_volume(resolution, S)
-            if not self.opt.sdf:      # the occupancy grid as a baseline mask (also excludes untrained regions), :509-516
-                mask = F.interpolate(self._grid_as_volume(0)[None, None], size=[resolution] * 3, mode="nearest")[0, 0]
-                sigmas = sigmas * (mask > density_thresh)
-        sigmas = torch.nan_to_num(sigmas, 0)
-        if self.opt.sdf:
-            vertices, triangles = marching_cubes(-sigmas, 0.0, div=resolution - 1.0, mul=2.0, add=-1.0)
-        else:
-            vertices, triangles = marching_cubes(sigmas, density_thresh, div=resolution - 1.0, mul=2.0, add=-1.0)
+            if resolution == self.grid_size:
+                sigmas = self._grid_as_volume(0)
+            else:
+                sigmas = self.density_volume(resolution, S)
+                if not self.opt.sdf:      # the occupancy grid as a baseline mask (also excludes untrained regions), :509-516
+                    mask = F.interpolate(self._grid_as_volume(0)[None, None], size=[resolution] * 3, mode="nearest")[0, 0]
+                    sigmas = sigmas * (mask > density_thresh)
+            sigmas = torch.nan_to_num(sigmas, 0)
+            if self.opt.sdf:
+                vertices, triangles = marching_cubes(-sigmas, 0.0, div=resolution - 1.0, mul=2.0, add=-1.0)
+            else:
+                vertices, triangles = marching_cubes(sigmas, density_thresh, div=resolution - 1.0, mul=2.0, add=-1.0)
         if dataset is not None and triangles.shape[0] > 0:
             unseen = self.mark_unseen_triangles(vertices, triangles, dataset.mvps, dataset.H, dataset.W)
             vertices, triangles = export.remove_faces(vertices, triangles, unseen, dilation=getattr(self.opt, "visibility_mask_dilation", 5))
@@ -650,6 +670,25 @@ class NeRFRenderer(nn.Module):
                 meshes[1] = shell
                 export.write_ply(os.path.join(save_path, "mesh_1.ply"), shell[0].cpu().numpy(), shell[1].cpu().numpy())
         return meshes
+
+    def _tsdf_inner_mesh(self, resolution, capture, kw):
+        """The inner mesh of export_stage0(method="tsdf"): the inference render's depth at every view of `capture`, fused into a
+        TSDFVolume(resolution) on the unit box (tsdf.fuse_views), and its zero level set (TSDFVolume.extract).  kw: the keywords of
+        TSDFVolume, surface_depth and fuse_views, told apart by name."""
+        from . import tsdf as T
+        from .metrics import field_renderer
+        kw = dict(kw or {})
+        unknown = set(kw) - {"trunc", "w_max", "min_depth", "alpha_min", "carve", "alpha_carve", "chunk"}
+        if unknown:
+            raise ValueError(f"export_stage0: unknown tsdf option(s) {sorted(unknown)}")
+        vol_kw = {k: kw.pop(k) for k in ("trunc", "w_max", "min_depth") if k in kw}
+        was_training = self.training
+        volume = T.TSDFVolume(int(resolution), device=self.density_bitfield.device, **vol_kw)
+        try:
+            T.fuse_views(field_renderer(self, capture), capture, volume, **kw)
+        finally:
+            self.train(was_training)            # field_renderer puts the model into eval mode
+        return volume.extract()
 
     def _sdf_outer_shell(self, resolution, S, dec_target, dataset, clean):
         """The contracted background of the SDF recipe as a world-space mesh (nerf/renderer.py:548-601, in its order), or None when a

@@ -7,6 +7,7 @@
     tools/evaluate.py --patch_size 16 [--lambda_patch_ssim w] [--field_only]                stage 0 on patch batches (the autograd trainer)
     tools/evaluate.py --lambda_distort w [--distort_space disparity] [--field_only]         stage 0 with the distortion loss (the autograd trainer)
     tools/evaluate.py --data PATH --optimize_poses [--lr_pose r]                            stage 0 refines the camera poses (writes OUT/poses_refined.npy)
+    tools/evaluate.py --data PATH --mesh_method tsdf [--tsdf_trunc d] [--tsdf_carve]       the stage-0 mesh by TSDF fusion of rendered depth
 
 With a checkpoint of the needed stage in OUT/checkpoints (--ckpt, default latest) the model is loaded instead of trained:
 --iters0 0 / --iters1 0 are then legal, and the stage-1 file brings its mesh with it.
@@ -21,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from nerf2mesh_amd import checkpoint, export, metrics, synthetic as S
+from nerf2mesh_amd import checkpoint, export, metrics, synthetic as S, tsdf
 from nerf2mesh_amd.asset import ExportedAsset
 from nerf2mesh_amd.capture import Capture
 from nerf2mesh_amd.engine import Stage0Engine
@@ -50,18 +51,24 @@ ap.add_argument("--lambda_distort", type=float, default=0.0, help="stage 0: weig
 ap.add_argument("--distort_space", choices=["linear", "disparity"], default="linear", help="--lambda_distort: normalise the sample intervals in t or in 1 / t")
 ap.add_argument("--optimize_poses", action="store_true", help="stage 0: train a correction per camera next to the field (needs --data; the autograd trainer, unfused field)")
 ap.add_argument("--lr_pose", type=float, default=1e-3, help="--optimize_poses: learning rate of the corrections")
+ap.add_argument("--mesh_method", choices=["density", "tsdf"], default="density", help="the stage-0 mesh: an iso-surface of the density lattice, or TSDF fusion of the depth rendered at every training camera (DESIGN 4.32; needs --data; not a reference option)")
+ap.add_argument("--tsdf_trunc", type=float, default=0.0, help="--mesh_method tsdf: truncation distance in world units (0: four lattice spacings)")
+ap.add_argument("--tsdf_carve", action="store_true", help="--mesh_method tsdf: rays that stop at nothing mark the points along them as empty")
 ap.add_argument("--ckpt", default="latest", help="latest | scratch | best | PATH: a trained model of OUT/checkpoints instead of training")
 ap.add_argument("--field_only", action="store_true", help="stop after the field's evaluation (no mesh, no stage 1, no export)")
 args = ap.parse_args()
 if args.optimize_poses and args.data is None:
     ap.error("--optimize_poses needs --data (the synthetic scene's poses are exact)")
+if args.mesh_method == "tsdf" and args.data is None:
+    ap.error("--mesh_method tsdf needs --data (the depth maps are rendered at a captured set's cameras)")
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 
 opt = make_options(O=True, bound=1, dt_gamma=0, iters=args.iters0, fused_mlp=not args.optimize_poses, lambda_ssim=args.lambda_ssim, data_format=args.data_format,
                    patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, lambda_distort=args.lambda_distort,
                    distort_space=args.distort_space, optimize_poses=args.optimize_poses, lr_pose=args.lr_pose,
-                   per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort, workspace=args.out)
+                   per_view_intrinsics=args.data_format == "dtu", undistort=args.undistort, workspace=args.out,
+                   mesh_method=args.mesh_method, tsdf_trunc=args.tsdf_trunc, tsdf_carve=args.tsdf_carve)
 model = NeRFNetwork(opt)
 if args.data is None:
     cap, poses = None, S.make_cameras(100, seed=0)
@@ -129,7 +136,8 @@ if saved_mesh is not None:              # the stage-1 file brings its mesh with 
     tr = Stage1Trainer(model, opt, poses, saved_mesh[0], rt, dev, capture=cap, v_cumsum=saved_mesh[2], f_cumsum=saved_mesh[3])
 else:
     with eng.averaged_parameters():
-        model.export_stage0(os.path.join(args.out, "mesh_stage0"), resolution=args.resolution, **({} if cap is None else dict(dataset=cap, clean=True, decimate=True)))
+        model.export_stage0(os.path.join(args.out, "mesh_stage0"), resolution=args.resolution, **({} if cap is None else dict(dataset=cap, clean=True, decimate=True)),
+                            **tsdf.export_options(opt))
     rv, rt = export.read_ply(os.path.join(args.out, "mesh_stage0", "mesh_0.ply"))
     tr = Stage1Trainer(model, opt, poses, torch.from_numpy(rv), torch.from_numpy(rt), dev, capture=cap)
 drv = Stage1Engine(tr) if Stage1Engine.supported(tr) else tr

@@ -48,7 +48,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from nerf2mesh_amd import checkpoint
+from nerf2mesh_amd import checkpoint, tsdf
 from nerf2mesh_amd.asset import ExportedAsset, evaluate_export, psnr
 from nerf2mesh_amd.capture import Capture
 from nerf2mesh_amd.engine import Stage0Engine
@@ -88,6 +88,9 @@ ap.add_argument("--lambda_distort", type=float, default=0.0, help="stage 0: weig
 ap.add_argument("--distort_space", choices=["linear", "disparity"], default="linear", help="--lambda_distort: normalise the sample intervals in t or in 1 / t")
 ap.add_argument("--optimize_poses", action="store_true", help="stage 0: train a correction (rotation, translation) per camera next to the field (not a reference option; the autograd trainer, unfused field)")
 ap.add_argument("--lr_pose", type=float, default=1e-3, help="--optimize_poses: learning rate of the corrections")
+ap.add_argument("--mesh_method", choices=["density", "tsdf"], default="density", help="the stage-0 mesh: an iso-surface of the density lattice, or TSDF fusion of the depth rendered at every training camera (DESIGN 4.32; not a reference option)")
+ap.add_argument("--tsdf_trunc", type=float, default=0.0, help="--mesh_method tsdf: truncation distance in world units (0: four lattice spacings)")
+ap.add_argument("--tsdf_carve", action="store_true", help="--mesh_method tsdf: rays that stop at nothing mark the points along them as empty")
 ap.add_argument("--test", action="store_true", help="after training, render a test-time camera path from the stage-1 mesh into WORKSPACE/results")
 ap.add_argument("--test_no_video", action="store_true", help="--test: frames only, no animated PNGs")
 ap.add_argument("--camera_traj", choices=["", "circle"], default="", help="--test: the path (default: interpolate between random training views)")
@@ -115,6 +118,8 @@ if args.enable_sparse_depth and args.enable_dense_depth:
     ap.error("--enable_sparse_depth and --enable_dense_depth exclude each other")
 if args.optimize_poses and args.sdf:
     ap.error("--optimize_poses does not run with --sdf")
+if args.mesh_method == "tsdf" and args.sdf:
+    ap.error("--mesh_method tsdf does not run with --sdf (the SDF recipe already meshes a signed distance)")
 
 
 def clock(label, t0, extra=""):
@@ -153,7 +158,8 @@ opt = make_options(O=True, bound=args.bound, dt_gamma=0 if args.bound <= 1 else 
                    enable_cam_near_far=args.enable_cam_near_far, per_view_intrinsics=args.per_view_intrinsics, undistort=args.undistort,
                    lambda_depth=args.lambda_depth, ind_dim=args.ind_dim, ind_num=args.ind_num, sdf=args.sdf,
                    patch_size=args.patch_size, lambda_patch_ssim=args.lambda_patch_ssim, lambda_distort=args.lambda_distort,
-                   distort_space=args.distort_space, optimize_poses=args.optimize_poses, lr_pose=args.lr_pose, camera_traj=args.camera_traj)
+                   distort_space=args.distort_space, optimize_poses=args.optimize_poses, lr_pose=args.lr_pose, camera_traj=args.camera_traj,
+                   mesh_method=args.mesh_method, tsdf_trunc=args.tsdf_trunc, tsdf_carve=args.tsdf_carve)
 model = NeRFNetwork(opt)
 if colmap:
     model.to(dev)
@@ -191,9 +197,9 @@ saved_mesh = checkpoint.stage1_mesh(args.workspace, args.ckpt)          # a stag
 if saved_mesh is None:
     with eng.averaged_parameters():          # the mesh comes from the averaged weights, like the reference's (nerf/utils.py:1340-1341)
         meshes = model.export_stage0(os.path.join(args.workspace, "mesh_stage0"), resolution=args.resolution, decimate_target=args.decimate_target,
-                                     dataset=cap, clean=True, decimate=True)
+                                     dataset=cap, clean=True, decimate=True, **tsdf.export_options(opt))
     v0, f0 = meshes[0]
-    clock("export_stage0", t0, f"{v0.shape[0]} vertices, {f0.shape[0]} triangles (visibility filter, clean, decimate)")
+    clock("export_stage0", t0, f"{v0.shape[0]} vertices, {f0.shape[0]} triangles ({'TSDF fusion, ' if opt.mesh_method == 'tsdf' else ''}visibility filter, clean, decimate)")
     if f0.shape[0] == 0:
         raise SystemExit("export_stage0 left no face: stage 0 has not found the object (more --iters0, or check --scale / --bound)")
 
